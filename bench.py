@@ -4,6 +4,12 @@
 Contract (see the driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 it is launched by
 torch.distributed.run, one rank per GPU.
 
+A PLAIN run does what the headline needs and nothing else: it stages ONE file of the configuration's reads (PLAIN_TEXT_BYTES
+of FASTQ text -- C2: 199 000 of its 4 M reads; `--e2e-reads` asks for more, all of them included), runs the command line over
+it W + K times and prints the line.  `--dump-outputs DIR` also writes what the last timed run produced as DIR/*.npy.
+Everything else -- the reference binary on the same file (`cpu_baseline`), the /dev/null sink, the three-ranks-on-one-GPU
+leg, the pinned variant, the kernel path with its `roofline`, the link measurement -- runs with `--full`.
+
 STDOUT carries ONE line of at most 4 kB (the contract's keys, `roofline`, `cpu_baseline`, the speed-up, `scaling_figures`);
 everything else this program measures goes to `--detail-file` (default: bench_detail.json beside this file) and to stderr.
 
@@ -49,6 +55,11 @@ REF = os.path.join(ROOT, "oracle", "_ref", "tgsfilter_ref")
 # returns ("sync"); TGSF_DETACH=1 makes it work in a child whose teardown goes on after the caller has its status.
 DEFAULT_EXIT_MODE = "sync"
 FQ_MULTISET = os.path.join(ROOT, "tools", "fq_multiset")
+# FASTQ text a run stages when --e2e-reads does not say how many reads: what 16 CPUs write in a few seconds, so that a plain
+# run spends its time in its steps (all of C2 is 360 GB: minutes of generation before the first step)
+PLAIN_TEXT_BYTES = 18e9
+KEEP_OUTPUTS = 16            # outputs of finished runs left on tmpfs at most before they are removed together, a thread each
+DUMP_WINDOWS, DUMP_WINDOW_BYTES = 1024, 8192      # --dump-outputs: 8 MB of the output text (32 MB as float32)
 
 
 def log(*a):
@@ -266,8 +277,64 @@ def multiset_of(paths):
     return [str(x) for x in tot]
 
 
+def remove_together(paths):
+    """Removes several tmpfs files at once, a thread each: freeing the pages of ONE file is one thread's work in the
+    kernel (seconds for tens of GB), several files are freed side by side."""
+    import threading
+    ts = [threading.Thread(target=os.remove, args=(p,)) for p in paths]
+    for t in ts:
+        t.start()
+    for t in ts:
+        t.join()
+
+
+def dump_outputs(dump_dir, paths, stderr_text):
+    """--dump-outputs: what the caller of the last timed run received, as float arrays two builds can be compared by.
+      output_digest.npy  float64[10]  records, bytes, and the order-independent sum and xor of the record hashes
+                                      (tools/fq_multiset.c) as four 16-bit limbs each, low limb first;
+      output_sample.npy  float32      the bytes of the output text (the parts of a sharded run taken as one text, in
+                                      rank order): all of it when it is small, else DUMP_WINDOWS windows of
+                                      DUMP_WINDOW_BYTES -- the first, the last and seeded positions between them.  The
+                                      records come in input order, so the same input gives the same text;
+      info_text.npy      float32      the bytes of the INFO lines (trims, identified adapters, depths, counters);
+      info_numbers.npy   float64      the numbers in those lines, in order."""
+    os.makedirs(dump_dir, exist_ok=True)
+    m = [int(x) for x in multiset_of(paths)]
+    limbs = lambda v: [float((v >> (16 * i)) & 0xffff) for i in range(4)]
+    np.save(os.path.join(dump_dir, "output_digest.npy"), np.array([float(m[0]), float(m[3])] + limbs(m[1]) + limbs(m[2]), dtype=np.float64))
+    sizes = [os.path.getsize(p) for p in paths]
+    total = sum(sizes)
+    win = min(DUMP_WINDOW_BYTES, total)
+    rng = np.random.default_rng(20240607)
+    if total <= DUMP_WINDOWS * DUMP_WINDOW_BYTES:      # a small output: all of it
+        at, win = np.array([0]), total
+    else:
+        at = np.unique(np.concatenate([[0, total - win], (rng.random(DUMP_WINDOWS - 2) * (total - win + 1)).astype(np.int64)]))
+    text = bytearray()
+    files = [open(p, "rb") for p in paths]
+    try:
+        for a in at:
+            a, left = int(a), win
+            for f, n in zip(files, sizes):               # a window may run from one part into the next
+                if a < n and left:
+                    f.seek(a)
+                    got = f.read(min(left, n - a))
+                    text += got
+                    left -= len(got)
+                    a = n
+                a -= n
+    finally:
+        for f in files:
+            f.close()
+    np.save(os.path.join(dump_dir, "output_sample.npy"), np.frombuffer(bytes(text), dtype=np.uint8).astype(np.float32))
+    info = "\n".join(info_lines(stderr_text))
+    np.save(os.path.join(dump_dir, "info_text.npy"), np.frombuffer(info.encode(), dtype=np.uint8).astype(np.float32))
+    np.save(os.path.join(dump_dir, "info_numbers.npy"), np.array([float(x) for x in re.findall(r"-?\d+(?:\.\d+)?(?:[eE][-+]?\d+)?", info)], dtype=np.float64))
+    log("bench: outputs of the last timed run (%d records, %d bytes) written to %s" % (m[0], m[3], dump_dir))
+
+
 def e2e_leg(args, n_gpus):
-    """The command line end to end on the configuration's reads (default: C2's 4 M), staged on tmpfs as ONE file when the
+    """The command line end to end on the configuration's reads (`--e2e-reads`; C2 has 4 M), staged on tmpfs as ONE file when the
     box's memory holds input + output, as CONSECUTIVE files (same generator, seeds in a row) otherwise -- C2 as written is
     360 GB of text + 215 GB of output, more than the box's memory control group allows at once.
     A STEP = one run of the command line over ONE staged file (C2 on this pool: a third of the 4 M reads, 60 Gbases, 120 GB
@@ -284,8 +351,11 @@ def e2e_leg(args, n_gpus):
                (-t min(cpu.max - 1, 32)), REF_RUNS run(s) each; on the other files once, at the faster of the two.  Output
                multisets and INFO lines compared with ours for every file;
     then, on the first file only and budget permitting: the /dev/null sink, and (N = 1) the same run as 3 rank processes
-    sharing the GPU with a part file each (`sharded`: the program path of N GPUs on this box)."""
+    sharing the GPU with a part file each (`sharded`: the program path of N GPUs on this box).
+    Without `--full` only `ours` runs; without `--e2e-reads` the reads are what makes PLAIN_TEXT_BYTES of text."""
     from tgsfilter_amd import synth
+    full = bool(getattr(args, "full", True))           # (a caller with arguments of its own that does not say: every leg, as before --full was)
+    dump_dir = getattr(args, "dump_outputs", None)
     if not os.path.exists(CLI):
         raise SystemExit("bench.py: %s is missing -- run __graft_entry__.build() (there is no fallback path)" % CLI)
     budget = Budget(float(getattr(args, "e2e_budget_s", 1500.0)))
@@ -293,8 +363,8 @@ def e2e_leg(args, n_gpus):
     if shm and shutil.disk_usage(shm).free < (1 << 30) and shutil.disk_usage(tempfile.gettempdir()).free > shutil.disk_usage(shm).free:
         shm = None                                    # a token /dev/shm (container default of 64 MB): stage on the temporary directory
     cfg = E2E_CONFIGS[getattr(args, "config", "c2") or "c2"]
-    n_want = n_reads = args.e2e_reads if getattr(args, "e2e_reads", None) else cfg["reads"]
     per_read = cfg["per_read"]                        # bytes of text per read (2 x mean length + header)
+    n_want = n_reads = args.e2e_reads if getattr(args, "e2e_reads", None) else min(cfg["reads"], int(PLAIN_TEXT_BYTES // per_read) // 1000 * 1000)
     # Room for the staging: the input and ONE output at a time live on tmpfs (ours is digested and removed before the
     # reference writes its own); an output is never larger than its input.  tmpfs pages are memory of the box's control
     # group: a group that outgrows memory.max loses the whole box, so stay well inside it.
@@ -344,7 +414,11 @@ def e2e_leg(args, n_gpus):
     env = dict(os.environ, TGSF_TIMING="1")
     env.pop("TGSF_SYNC_EXIT", None)
     env.pop("TGSF_DETACH", None)
-    have_ref = os.path.exists(REF) and not args.no_cpu_baseline
+    have_ref = full and os.path.exists(REF) and not args.no_cpu_baseline
+    # outputs of finished runs stay on tmpfs while they fit beside the input and the next output (a small file: three tenths
+    # of the room), and go together; at C2's own size the room holds the input and ONE output, and each goes before the next run
+    spare = 0.3 * free if need <= 0.15 * free else 0.0
+    retired = []
     want_ranks = int(getattr(args, "e2e_ranks", 0) or 0) or (n_gpus if n_gpus > 1 else 0)
     rank_devs = devs if n_gpus > 1 else "0"
 
@@ -362,6 +436,19 @@ def e2e_leg(args, n_gpus):
         phase["digests"] += time.perf_counter() - t0
         return m
 
+    def flush():
+        t0 = time.perf_counter()
+        remove_together([p for p in retired if os.path.isfile(p) and not os.path.islink(p)])
+        del retired[:]
+        phase["remove_outputs"] += time.perf_counter() - t0
+
+    def retire(out, ranks, next_bytes):
+        """A finished run's output: removed now, or with the others once the room for them is used up."""
+        retired.extend(out_files(out, ranks))
+        held = sum(os.path.getsize(p) for p in retired if os.path.isfile(p) and not os.path.islink(p))
+        if held + next_bytes > spare or len(retired) >= KEEP_OUTPUTS:
+            flush()
+
     def ours(fq, out, flags, ranks=0, rdevs=None):
         rm(out)
         how = ["--ranks", str(ranks), "--devices", rdevs or rank_devs] if ranks else ["--devices", devs]
@@ -375,14 +462,22 @@ def e2e_leg(args, n_gpus):
         phase["reference"] += r[0]
         return r
 
-    def timed(fq, out, flags, warm, k, ranks=0, rdevs=None):
-        for _ in range(warm):
-            ours(fq, out, flags, ranks, rdevs)
+    def timed(fq, out, flags, warm, k, ranks=0, rdevs=None, own_names=False):
+        """`warm` untimed and `k` timed runs.  own_names: every run writes a file of its own name (<out less .fq>.<j>.fq: the
+        suffix decides the format) and the finished ones are retire()d, so that no removal stands between two runs
+        unless the room is used up; the last run's output is left under `out` for the caller."""
         walls, err, cpu = [], "", []
-        for _ in range(k):
-            dt, err = ours(fq, out, flags, ranks, rdevs)
-            walls.append(dt)
-            cpu.append(dict(LAST_RUN_CPU))
+        for j in range(warm + k):
+            o = "%s.%d.fq" % (out[:-3], j) if own_names else out
+            dt, err = ours(fq, o, flags, ranks, rdevs)
+            if j >= warm:
+                walls.append(dt)
+                cpu.append(dict(LAST_RUN_CPU))
+            if own_names and j < warm + k - 1:
+                retire(o, ranks, os.path.getsize(fq))
+            elif own_names:
+                for a, b in zip(out_files(o, ranks), out_files(out, ranks)):
+                    os.rename(a, b)
         return walls, err, cpu
 
     def out_files(out, ranks):
@@ -431,7 +526,8 @@ def e2e_leg(args, n_gpus):
                 % (f + 1, n_staged, per_file[f], bases / 1e9, nbytes / 1e9, fq, time.perf_counter() - t0, gen_procs))
             out_o, out_r = os.path.join(td, "ours.fq"), os.path.join(td, "ref.fq")
             rm0 = phase["remove_outputs"]
-            walls, err, cpu = timed(fq, out_o, flags, args.warmup if first else min(args.warmup, 1), steps_of[f], want_ranks)
+            walls, err, cpu = timed(fq, out_o, flags, args.warmup if first else min(args.warmup, 1), steps_of[f], want_ranks, own_names=True)
+            flush()
             s = describe(walls, err, bases)
             if first:
                 est["run_s"] = s["wall_s_mean"]
@@ -440,10 +536,15 @@ def e2e_leg(args, n_gpus):
             if want_ranks:
                 s["ranks"] = want_ranks
             info = info_lines(err)
+            if dump_dir and f == n_staged - 1:
+                t0 = time.perf_counter()
+                dump_outputs(dump_dir, out_files(out_o, want_ranks), err)
+                phase["digests"] += time.perf_counter() - t0
             mine = digest(out_files(out_o, want_ranks)) if have_ref else None
             if mine:
                 s["output_records"], s["output_bytes"] = int(mine[0]), int(mine[3])
-            rm(out_o)
+            if full:                                  # (a plain run is over with this file: its last output goes with the input)
+                rm(out_o)
             if have_ref:
                 # the reference on the same file, flags and sink.  First file: both thread counts, REF_RUNS runs each, as
                 # the budget allows (the first run's output and INFO lines are compared with ours); later files: once.
@@ -499,7 +600,7 @@ def e2e_leg(args, n_gpus):
                 for r in range(want_ranks):
                     os.symlink("/dev/null", "%s.part%d" % (null_out, r))
                 k_null = min(args.steps, 3)
-                if budget.allows("dev_null sink", (k_null + 1) * s["wall_s_mean"] + 5 + reserve(f)):
+                if full and budget.allows("dev_null sink", (k_null + 1) * s["wall_s_mean"] + 5 + reserve(f)):
                     w2, e2, _ = timed(fq, null_out, flags, min(args.warmup, 1), k_null, want_ranks)
                     d = describe(w2, e2, bases)
                     d["same_counters_as_the_file_run"] = info_lines(e2) == info
@@ -509,7 +610,7 @@ def e2e_leg(args, n_gpus):
                     log("bench: e2e dev_null: %s" % json.dumps({k2: v for k2, v in d.items() if k2 not in ("timing_line", "shard_lines")}))
                 # N = 1: the program path of N GPUs on this box -- rank processes sharing the GPU, a part file each (the tallies
                 # go over the ranks' sockets: RCCL refuses two ranks on one device).  Same records, same INFO lines.
-                if n_gpus == 1 and not want_ranks and getattr(args, "sharded_leg", True):
+                if full and n_gpus == 1 and not want_ranks and getattr(args, "sharded_leg", True):
                     k_sh = min(args.steps, 3)
                     for nr in (3,):
                         if not budget.allows("sharded leg, %d ranks on one GPU" % nr, (k_sh + 1) * s["wall_s_mean"] + 10 + reserve(f)):
@@ -525,7 +626,7 @@ def e2e_leg(args, n_gpus):
                             raise SystemExit("bench: the sharded run's records or INFO lines differ from the single process's")
                         sinks["tmpfs_part_files_%d_ranks_one_gpu" % nr] = d
                         log("bench: e2e sharded: %s" % json.dumps({k2: v for k2, v in d.items() if k2 not in ("timing_line", "shard_lines")}))
-            os.remove(fq)
+            remove_together([p for p in [fq] + out_files(out_o, want_ranks) if os.path.isfile(p)])
         # ---- the whole workload: a step = one pass over all the files ----
         step_walls = [w for s in files for w in s["wall_s"]]          # the K timed steps, in the order they ran
         K = len(step_walls)
@@ -563,7 +664,7 @@ def e2e_leg(args, n_gpus):
                "read by both programs through the page cache" % (shm or "tmp"), "sinks": sinks}
         # the pinned pre-pass on round 2's file, the reference beside it (opt-in since round 5: --pinned-variant)
         n_pin = min(400_000, n_reads)
-        if cfg is E2E_CONFIGS["c2"] and getattr(args, "pinned_variant", False) and budget.allows("pinned-pre-pass variant", 45 + n_pin * 1.1e-4):
+        if full and cfg is E2E_CONFIGS["c2"] and getattr(args, "pinned_variant", False) and budget.allows("pinned-pre-pass variant", 45 + n_pin * 1.1e-4):
             fq2 = os.path.join(td, "c2_400k.fq")
             bases2, nbytes2 = synth.write_ont_fastq(fq2, n_pin, seed=2, procs=gen_procs)
             fa = os.path.join(td, "rapid.fa")
@@ -1052,10 +1153,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3, help="timed end-to-end runs of the command line")
     ap.add_argument("--warmup", type=int, default=1, help="untimed end-to-end runs before them")
+    ap.add_argument("--full", action="store_true", help="also everything beside the headline: the reference binary on the same file (cpu_baseline, outputs "
+                    "compared), the /dev/null sink, three ranks sharing the GPU, the kernel path with its roofline, the link measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step produced as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--config", choices=sorted(E2E_CONFIGS), default="c2", help="BASELINE.json configuration of the end-to-end leg (c2: the headline; "
                     "c5: ultra-long reads, repeat gate and downsampling)")
-    ap.add_argument("--e2e-reads", type=int, default=None, help="reads in the end-to-end FASTQ file (default: the configuration's -- C2: 4 M reads, ~90 KB "
-                    "of text each); reduced -- and said so in config.workload -- to what the staging file system / the box's memory control group holds")
+    ap.add_argument("--e2e-reads", type=int, default=None, help="reads in the end-to-end FASTQ file (default: %d GB of text -- C2: 199 000 reads of ~90 KB; all of C2: "
+                    "--e2e-reads 4000000, which takes minutes to stage); reduced" % (PLAIN_TEXT_BYTES / 1e9) + " -- and said so in config.workload -- to what the staging file system / the box's memory control group holds")
     ap.add_argument("--e2e-budget-s", type=float, default=900.0, help="seconds the end-to-end leg may take: optional legs are dropped (and named in "
                     "e2e.skipped) when it runs short; the K timed steps never are")
     ap.add_argument("--pinned-variant", action="store_true", help="also run the pinned-pre-pass variant (-5 0 -3 0 -a rapid.fa on 400 000 reads: round 2's headline)")
@@ -1109,8 +1213,26 @@ def main():
     # cross-process sharing need this; a value already set stays.  Before torch / any child process is started.)
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
-    import torch
-    import torch.distributed as dist
+    # The library the command line loads, checked once by this process: it is there, speaks this ABI and is the HIP build
+    # (capi.load raises otherwise) -- a run is never timed on a stand-in.  Loading it starts nothing on the device.
+    # (Where this process goes on to use the GPU through torch, torch brings the device up first: it ships a HIP runtime
+    # of its own, and the library binds the system's.)
+    def check_library():
+        from tgsfilter_amd import capi
+        lib = capi.load()
+        d = {"path": os.environ.get("TGSF_LIB") or capi.DEFAULT_LIB, "abi_version": int(lib.tgsf_abi_version()), "backend": lib.tgsf_backend().decode()}
+        log("bench: libtgsf: %s" % json.dumps(d))
+        return d
+
+    library = None
+    # a plain run on one GPU is the command line's runs and nothing of this process on the GPU: no torch
+    want_kernel_path = (args.full or args.no_e2e) and not args.no_kernel_path
+    torch = dist = None
+    if world > 1 or want_kernel_path or args.full:
+        import torch
+        import torch.distributed as dist
+    if not (want_kernel_path or args.full):
+        library = check_library()
     host_group = None
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -1132,11 +1254,14 @@ def main():
         if world > 1:
             dist.barrier(group=host_group)
 
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
-    torch.cuda.set_device(local_rank)
-    device = torch.device("cuda", local_rank)
-    xdev = device if args.backend == "nccl" else None
+    device = xdev = None
+    if want_kernel_path or args.full:
+        if not torch.cuda.is_available():
+            raise SystemExit("bench.py needs an MI355X: the HIP path has no CPU fallback")
+        torch.cuda.set_device(local_rank)
+        device = torch.device("cuda", local_rank)
+        xdev = device if args.backend == "nccl" else None
+        library = check_library()
 
     kp = roofline = None
     if e2e and args.head_trim is None and args.tail_trim is None:
@@ -1150,12 +1275,12 @@ def main():
         box = [args.head_trim, args.tail_trim]
         dist.broadcast_object_list(box, src=0, group=host_group)
         args.head_trim, args.tail_trim = box
-    if not args.no_kernel_path:
+    if want_kernel_path:
         kp, roofline = kernel_leg(args, torch, dist, world, rank, local_rank, device, xdev, host_group)
 
     # the roof the end-to-end run sits under at one GPU: the link to the device (the text goes over it once)
     link = None
-    if rank == 0 and e2e:
+    if rank == 0 and e2e and args.full and device is not None:
         link = h2d_peak(torch, device)
 
     if rank == 0:
@@ -1189,6 +1314,7 @@ def main():
                        "parallelism": ("%d rank processes, one per GPU: byte-range shards of the input, part files, one all-reduce of the tallies" % world) if world > 1
                                       else "one GPU (three contexts / feeder threads); reads shard over rank processes with tgsfilter --ranks N"},
         }
+        out["library"] = library
         if e2e:
             out["e2e"] = e2e
             s = e2e["sinks"]["tmpfs_file"]

@@ -6,8 +6,15 @@ import gzip
 import json
 import os
 import re
+import shutil
 import subprocess
 import tempfile
+
+
+def socket_dir() -> str:
+    """A directory for a unix socket of a test: a socket's name is at most 107 bytes, and the temporary directory of a
+    test run (TMPDIR, pytest's tmp_path) may be longer than that.  The caller removes it."""
+    return tempfile.mkdtemp(prefix="tgsf_rdv_", dir="/tmp")
 
 
 def shardable(golden_dir: str, name: str) -> bool:
@@ -54,9 +61,13 @@ def run_case(binary: str, golden_dir: str, name: str, extra_args=(), compress=No
             args += ["-a", fa]
         out_name = os.path.join(td, "out.fa" if fmt == "fa" else "out.fq")
         if ranks and launcher == "external":
-            procs = [subprocess.Popen(args + ["--shard", "%d/%d" % (r, ranks), "--rendezvous", os.path.join(td, "rdv.sock")],
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=td) for r in range(ranks)]
-            outs = [q.communicate(timeout=600) for q in procs]
+            sd = socket_dir()
+            try:
+                procs = [subprocess.Popen(args + ["--shard", "%d/%d" % (r, ranks), "--rendezvous", os.path.join(sd, "rdv.sock")],
+                                          stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=td) for r in range(ranks)]
+                outs = [q.communicate(timeout=600) for q in procs]
+            finally:
+                shutil.rmtree(sd, ignore_errors=True)
             err = b"".join(o[1] for o in outs).decode().replace(td + "/", "")
             assert all(q.returncode == 0 for q in procs), err
         else:

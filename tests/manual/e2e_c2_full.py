@@ -20,7 +20,7 @@ for cmd in ("uname -r", "nproc", "df -h /dev/shm /tmp", "free -g", "cat /sys/ker
             "numactl -H", "cat /proc/sys/vm/overcommit_memory", "ulimit -l", "ulimit -n"):
     p = subprocess.run(cmd, shell=True, capture_output=True)
     print("$ %s\n%s" % (cmd, (p.stdout + p.stderr).decode().strip()), flush=True)
-args = types.SimpleNamespace(e2e_reads=reads, steps=steps, warmup=warmup, no_cpu_baseline=os.environ.get("NO_REF") == "1",
+args = types.SimpleNamespace(full=True, e2e_reads=reads, steps=steps, warmup=warmup, no_cpu_baseline=os.environ.get("NO_REF") == "1",
                              e2e_budget_s=float(os.environ.get("BUDGET_S", "3000")),
                              no_pinned_variant=os.environ.get("NO_PINNED") == "1")
 r = bench.e2e_leg(args, 1)

@@ -27,14 +27,14 @@ def test_header_symbols_exported(lib):
     assert lib.tgsf_abi_version() == abi.ABI_VERSION
 
 
-def test_struct_layout_matches_header():
+def test_struct_layout_matches_header(tmp_path):
     """sizeof() of the ctypes mirrors == what the C compiler sees."""
     src = r'''
     #include <stdio.h>
     #include "tgsf.h"
     int main(void){ printf("%zu %zu %zu %zu %zu\n", sizeof(tgsf_params), sizeof(tgsf_batch_in),
         sizeof(tgsf_batch_out), sizeof(tgsf_read_result), sizeof(tgsf_fragment)); return 0; }'''
-    exe = "/tmp/tgsf_sizes"
+    exe = str(tmp_path / "tgsf_sizes")             # (not a fixed name in /tmp: another user's file of that name cannot be written over)
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     out = subprocess.run([exe], capture_output=True, check=True).stdout.split()
     got = [int(x) for x in out]

@@ -15,7 +15,7 @@ def test_e2e_leg_with_the_emulated_cli(monkeypatch):
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tgsfilter_amd", "host"), "emul"], check=True)
     import bench
     monkeypatch.setattr(bench, "CLI", os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"))
-    args = types.SimpleNamespace(e2e_reads=16, steps=1, warmup=0, no_cpu_baseline=False, pinned_variant=True)
+    args = types.SimpleNamespace(full=True, e2e_reads=16, steps=1, warmup=0, no_cpu_baseline=False, pinned_variant=True)
     r = bench.e2e_leg(args, 1)
     s = r["sinks"]["tmpfs_file"]
     assert s["same_counters"] and s["gbases_per_s"] > 0 and s["reference_gbases_per_s"] > 0
@@ -43,7 +43,7 @@ def test_e2e_leg_over_several_files_and_as_rank_processes(monkeypatch):
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tgsfilter_amd", "host"), "emul"], check=True)
     import bench
     monkeypatch.setattr(bench, "CLI", os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"))
-    args = types.SimpleNamespace(e2e_reads=25, e2e_files=3, steps=4, warmup=1, no_cpu_baseline=False, sharded_leg=False)
+    args = types.SimpleNamespace(full=True, e2e_reads=25, e2e_files=3, steps=4, warmup=1, no_cpu_baseline=False, sharded_leg=False)
     r = bench.e2e_leg(args, 1)
     s = r["sinks"]["tmpfs_file"]
     assert r["files"] == 3 and r["reads_per_file"] == [9, 8, 8] and r["reads"] == 25 and len(s["per_file"]) == 3
@@ -57,10 +57,10 @@ def test_e2e_leg_over_several_files_and_as_rank_processes(monkeypatch):
     assert abs(s["reference_wall_s"] - sum(f["reference_wall_s"] for f in s["per_file"])) < 1e-9 and s["speedup_vs_reference"] > 0
     assert "tmpfs_part_files_3_ranks_one_gpu" not in r["sinks"]
     # fewer steps than files: only as many files are staged as there are steps
-    args = types.SimpleNamespace(e2e_reads=25, e2e_files=3, steps=2, warmup=0, no_cpu_baseline=False, sharded_leg=False)
+    args = types.SimpleNamespace(full=True, e2e_reads=25, e2e_files=3, steps=2, warmup=0, no_cpu_baseline=False, sharded_leg=False)
     r = bench.e2e_leg(args, 1)
     assert r["files"] == 2 and r["files_of_config_split"] == 3 and r["reads"] == 17 and r["steps_per_file"] == [1, 1]
-    args = types.SimpleNamespace(e2e_reads=20, e2e_ranks=2, steps=1, warmup=0, no_cpu_baseline=False)
+    args = types.SimpleNamespace(full=True, e2e_reads=20, e2e_ranks=2, steps=1, warmup=0, no_cpu_baseline=False)
     r = bench.e2e_leg(args, 1)
     s = r["sinks"]["tmpfs_file"]
     assert r["ranks"] == 2 and s["ranks"] == 2 and s["same_counters"] and s["same_output_multiset"] and len(s["per_file"][0]["shard_lines"]) == 2
@@ -73,7 +73,7 @@ def test_e2e_leg_config_c5_with_the_emulated_cli(monkeypatch):
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tgsfilter_amd", "host"), "emul"], check=True)
     import bench
     monkeypatch.setattr(bench, "CLI", os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"))
-    args = types.SimpleNamespace(e2e_reads=10, steps=1, warmup=0, no_cpu_baseline=False, config="c5")
+    args = types.SimpleNamespace(full=True, e2e_reads=10, steps=1, warmup=0, no_cpu_baseline=False, config="c5")
     r = bench.e2e_leg(args, 1)
     s = r["sinks"]["tmpfs_file"]
     assert r["flags"] == "-x ont -l 1000 -q 10 -g 3g -d 40 -p 100 -k 11" and "C5" in r["config"]
@@ -86,7 +86,7 @@ def test_e2e_leg_config_c3_with_the_emulated_cli(monkeypatch):
     subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tgsfilter_amd", "host"), "emul"], check=True)
     import bench
     monkeypatch.setattr(bench, "CLI", os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"))
-    args = types.SimpleNamespace(e2e_reads=40, steps=1, warmup=0, no_cpu_baseline=False, config="c3")
+    args = types.SimpleNamespace(full=True, e2e_reads=40, steps=1, warmup=0, no_cpu_baseline=False, config="c3")
     r = bench.e2e_leg(args, 1)
     s = r["sinks"]["tmpfs_file"]
     assert r["flags"] == "-x hifi -l 1000 -q 20 -M 35 -T 50" and "C3" in r["config"]

@@ -225,13 +225,16 @@ def test_cli_sharded_refusals(binary, golden_dir, tmp_path):
     raw = gzip.open(os.path.join(golden_dir, "ont_zoo.in.fq.gz"), "rb").read()
     fin = tmp_path / "in.fq"
     fin.write_bytes(raw)
-    gz = tmp_path / "in2.fq.gz"
+    import pathlib
+    import shutil
+    sockdir = pathlib.Path(cli_check.socket_dir())                    # (tmp_path may be too long for a socket's name)
+    gz = sockdir / "in2.fq.gz"
     gz.write_bytes(gzip.compress(raw))
     base = [binary, "-x", "ont", "-o", str(tmp_path / "o.fq")]
     for extra, what in ((["-i", str(gz), "--ranks", "2"], b"plain FASTQ"),
                         (["-i", str(fin), "--shard", "0/2"], b"--rendezvous"),
-                        (["-i", str(fin), "--shard", "2/2", "--rendezvous", str(tmp_path / "s")], b"no such rank"),
-                        (["-i", str(fin), "--ranks", "2", "--shard", "0/2", "--rendezvous", str(tmp_path / "s")], b"--ranks starts the ranks itself")):
+                        (["-i", str(fin), "--shard", "2/2", "--rendezvous", str(sockdir / "s")], b"no such rank"),
+                        (["-i", str(fin), "--ranks", "2", "--shard", "0/2", "--rendezvous", str(sockdir / "s")], b"--ranks starts the ranks itself")):
         p = subprocess.run(base + extra, capture_output=True, timeout=120)
         assert p.returncode != 0 and what in p.stderr, (extra, p.stderr)
     p = subprocess.run([binary, "-x", "ont", "-i", str(fin), "--ranks", "2"], capture_output=True, timeout=120)
@@ -239,6 +242,7 @@ def test_cli_sharded_refusals(binary, golden_dir, tmp_path):
     # a rendezvous path that names a file of the user's is refused, and the file is still there
     p = subprocess.run(base + ["-i", str(fin), "--shard", "0/2", "--rendezvous", str(gz)], capture_output=True, timeout=120)
     assert p.returncode != 0 and b"is not a socket" in p.stderr and gz.exists()
+    shutil.rmtree(sockdir, ignore_errors=True)
 
 
 def test_cli_shard_env_as_torchrun_sets_it(binary, golden_dir, tmp_path):
@@ -271,7 +275,9 @@ def test_cli_shard_a_live_rendezvous_socket_is_not_taken_away(binary, golden_dir
     import socket
     fin = tmp_path / "in.fq"
     fin.write_bytes(gzip.open(os.path.join(golden_dir, "ont_zoo.in.fq.gz"), "rb").read())
-    path = str(tmp_path / "rdv.sock")
+    import shutil
+    sockdir = cli_check.socket_dir()                                  # (tmp_path may be too long for a socket's name)
+    path = os.path.join(sockdir, "rdv.sock")
     live = socket.socket(socket.AF_UNIX, socket.SOCK_STREAM)
     live.bind(path)
     live.listen(4)
@@ -283,6 +289,7 @@ def test_cli_shard_a_live_rendezvous_socket_is_not_taken_away(binary, golden_dir
     r1 = subprocess.run(args[:-4] + ["--shard", "1/2", "--rendezvous", path], capture_output=True, timeout=300)
     err0 = q.communicate(timeout=300)[1]
     assert q.returncode == 0 and r1.returncode == 0, (err0[-1000:], r1.stderr[-1000:])
+    shutil.rmtree(sockdir, ignore_errors=True)
 
 
 def test_cli_sharded_job_ends_when_a_rank_fails(binary, golden_dir, tmp_path):

@@ -262,7 +262,7 @@ def test_bench_two_ranks_share_one_gpu_same_totals(tmp_path):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    common = ["--no-e2e", "--no-cpu-baseline", "--no-oracle-check", "--reads", "4096", "--kernel-warmup", "1", "--streams", "2"]
+    common = ["--full", "--no-e2e", "--no-cpu-baseline", "--no-oracle-check", "--reads", "4096", "--kernel-warmup", "1", "--streams", "2"]
     d1, d2 = str(tmp_path / "one.json"), str(tmp_path / "two.json")
     one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--kernel-steps", "6", "--detail-file", d1] + common, capture_output=True, timeout=900)
     assert one.returncode == 0, one.stderr.decode()[-2000:]
@@ -293,7 +293,7 @@ def test_bench_two_ranks_end_to_end_leg_runs_one_process_per_gpu(tmp_path):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("TGSF_DEBUG_KNOBS", None)                     # (the bench runs the product as a user would)
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", "29543", os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--backend", "gloo",
+                          "--master-port", "29543", os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--share-gpu", "--backend", "gloo",
                           "--e2e-reads", "3000", "--steps", "2", "--warmup", "1", "--no-kernel-path", "--detail-file", str(tmp_path / "d.json")],
                          capture_output=True, timeout=1200, env=env)
     assert two.returncode == 0, two.stderr.decode()[-3000:]

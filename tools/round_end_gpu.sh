@@ -6,11 +6,12 @@
 #                                          C2 and C3 with the pre-pass's trims, C5, 4 adapters), their traffic.json merged,
 #                                          the short-adapter shapes
 #   tools/round_end_gpu.sh ab <tag>        the clean-table A/B (tools/ab_clean.sh)
-#   tools/round_end_gpu.sh bench           the full bench line as the driver runs it + --config c3 + --config c5
+#   tools/round_end_gpu.sh bench           the full bench record (bench.py --full, all the reads of the configuration): C2, --config c3, --config c5
 #   tools/round_end_gpu.sh shard           rank processes sharing the one GPU against the single process (tests/manual/e2e_shard.py)
 cd $GRAFT_REPO_ROOT
 what=${1:-suite}; tag=${2:-r06}
 R=$GRAFT_REPO_ROOT
+O=${O:-$R/profile_out}      # the bench records go here (kept out of git)
 case $what in
 suite)
   python -m pytest tests -x -q -m gpu --durations=10 > gpurun_out/gpu_suite.txt 2>&1; tail -4 gpurun_out/gpu_suite.txt ;;
@@ -27,9 +28,11 @@ profile)
 ab)
   bash tools/ab_clean.sh > gpurun_out/${tag}_clean_tables_ab.txt 2>&1; head -30 gpurun_out/${tag}_clean_tables_ab.txt ;;
 bench)
-  python bench.py --gpus 1 --steps 20 --warmup 5 --detail-file gpurun_out/${tag}_bench_detail.json > gpurun_out/${tag}_bench_line.json 2> gpurun_out/bench.err; tail -c 600 gpurun_out/${tag}_bench_line.json
-  python bench.py --config c3 --steps 3 --warmup 1 --detail-file gpurun_out/${tag}_bench_c3_detail.json > gpurun_out/${tag}_bench_c3_line.json 2> gpurun_out/bench_c3.err; tail -c 400 gpurun_out/${tag}_bench_c3_line.json
-  python bench.py --config c5 --steps 2 --warmup 1 --detail-file gpurun_out/${tag}_bench_c5_detail.json > gpurun_out/${tag}_bench_c5_line.json 2> gpurun_out/bench_c5.err; tail -c 400 gpurun_out/${tag}_bench_c5_line.json ;;
+  # (the whole record: the reference beside ours, both sinks, the kernel path and its roofline; all of C2's reads)
+  mkdir -p $O
+  python bench.py --full --e2e-reads 4000000 --gpus 1 --steps 20 --warmup 5 --detail-file $O/${tag}_bench_detail.json > $O/${tag}_bench_line.json 2> $O/bench.err; tail -c 600 $O/${tag}_bench_line.json
+  python bench.py --full --e2e-reads 19000000 --config c3 --steps 3 --warmup 1 --detail-file $O/${tag}_bench_c3_detail.json > $O/${tag}_bench_c3_line.json 2> $O/bench_c3.err; tail -c 400 $O/${tag}_bench_c3_line.json
+  python bench.py --full --e2e-reads 1000000 --config c5 --steps 2 --warmup 1 --detail-file $O/${tag}_bench_c5_detail.json > $O/${tag}_bench_c5_line.json 2> $O/bench_c5.err; tail -c 400 $O/${tag}_bench_c5_line.json ;;
 shard)
   REPS=3 python tests/manual/e2e_shard.py 1333334 2 3 > gpurun_out/${tag}_shard_one_gpu.txt 2>&1; head -12 gpurun_out/${tag}_shard_one_gpu.txt ;;
 esac
