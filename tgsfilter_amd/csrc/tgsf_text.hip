@@ -1,0 +1,368 @@
+// tgsf_text.hip -- libtgsf_text.so: the record index of FASTQ / FASTA text on the device (include/tgsf_text.h).
+// Built on the public ABI of libtgsf only (tgsf_backend, tgsf_submit_device, tgsf_wait, tgsf_last_error).
+//
+// Built two ways from this one source, like tgsf_lib.hip:
+//   hipcc --offload-arch=gfx950  -ltgsf       -> tgsfilter_amd/libtgsf_text.so      (the product)
+//   g++ -x c++ -DTGSF_EMUL       -ltgsf_emul  -> tests/emul/libtgsf_text_emul.so    (serial emulation; test infrastructure)
+#include <stdarg.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#if defined(TGSF_EMUL)
+#include "tgsf_text_kernels.h"
+namespace tgsf_emul { thread_local Dim3 threadIdx, blockIdx, blockDim, gridDim; }
+typedef void* rt_stream;
+#include "tgsf_emul_rt.h"
+#else
+#include <hip/hip_runtime.h>
+#include "tgsf_text_kernels.h"
+typedef hipStream_t rt_stream;
+static int rt_malloc(void** p, size_t n) { return (int)hipMalloc(p, n ? n : 1); }
+static void rt_free(void* p) { (void)hipFree(p); }
+static int rt_memset(void* p, int v, size_t n, rt_stream s) { return (int)hipMemsetAsync(p, v, n, s); }
+static int rt_h2d(void* d, const void* s, size_t n, rt_stream st) { return (int)hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, st); }
+static int rt_d2h(void* d, const void* s, size_t n, rt_stream st) { return (int)hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, st); }
+static int rt_sync(rt_stream s) { return (int)hipStreamSynchronize(s); }
+static const char* rt_errstr(int e) { return hipGetErrorString((hipError_t)e); }
+#define TGSF_LAUNCH(kernel, grid, block, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (stream), __VA_ARGS__)
+#define TGSF_LAUNCH_COOP TGSF_LAUNCH
+static unsigned grid_cap(unsigned g) { return g; }
+#endif
+
+using namespace tgsf;
+
+static thread_local std::string g_create_error;
+
+struct tgsf_text {
+    int device;
+    uint64_t max_bytes, max_pieces;
+    uint32_t max_records;
+    rt_stream stream;
+    std::string error;
+    bool profile = false;
+    // device memory
+    uint8_t* d_text = nullptr;          // max_bytes rounded up to 16, + TGSF_TEXT_PAD
+    uint64_t* d_bits = nullptr;         // a bit per byte, whole pieces
+    uint32_t* d_cnt = nullptr;          // line ends per piece -> exclusive sums within blocks of kTextScanTile pieces
+    uint64_t* d_part = nullptr;         // ... and the blocks' offsets
+    uint64_t* d_table = nullptr;        // positions of the first 4 * max_records line ends
+    TextState* d_state = nullptr;
+    tgsf_text_index_arrays d_index = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    tgsf_text_summary* d_summary = nullptr;
+    // results of tgsf_text_submit before they go down
+    tgsf_read_result* d_reads = nullptr;
+    tgsf_fragment* d_frags = nullptr;
+    uint32_t frag_cap = 0;
+    uint32_t* d_nfrags = nullptr;
+    std::vector<void*> allocs;
+#if !defined(TGSF_EMUL)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool ev_recorded = false;
+#endif
+};
+
+static int fail(tgsf_text* tx, int code, const char* fmt, ...)
+{
+    char buf[768];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    if (tx) tx->error = buf; else g_create_error = buf;
+    return code;
+}
+
+template <class T>
+static int dev_alloc(tgsf_text* tx, T** p, size_t count)
+{
+    void* q = nullptr;
+    if (rt_malloc(&q, count * sizeof(T))) return 1;
+    tx->allocs.push_back(q);
+    *p = (T*)q;
+    return 0;
+}
+
+extern "C" int tgsf_text_abi_version(void) { return TGSF_TEXT_ABI_VERSION; }
+extern "C" const char* tgsf_text_backend(void) { return kTgsfEmul ? "emulation" : "hip:gfx950"; }
+extern "C" const char* tgsf_text_last_error(tgsf_text* tx) { return tx ? tx->error.c_str() : g_create_error.c_str(); }
+
+extern "C" void tgsf_text_destroy(tgsf_text* tx)
+{
+    if (!tx) return;
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+    if (tx->stream) { (void)hipStreamSynchronize(tx->stream); (void)hipStreamDestroy(tx->stream); }
+    for (hipEvent_t e : tx->ev) if (e) (void)hipEventDestroy(e);
+#endif
+    for (void* p : tx->allocs) rt_free(p);
+    delete tx;
+}
+
+extern "C" int tgsf_text_create(int device, uint64_t max_bytes, uint32_t max_records, tgsf_text** out)
+{
+    if (!out) return fail(nullptr, TGSF_E_INVALID, "null argument");
+    *out = nullptr;
+    if (max_bytes == 0 || max_records == 0) return fail(nullptr, TGSF_E_INVALID, "max_bytes and max_records must be positive");
+    // one build of the kernels per process: the product binds the HIP build of libtgsf, the emulation the emulation
+    const char* be = tgsf_backend();
+    if (strncmp(be, kTgsfEmul ? "emulation" : "hip", kTgsfEmul ? 9 : 3) != 0)
+        return fail(nullptr, TGSF_E_INVALID, "libtgsf_text (%s) is linked against the '%s' build of libtgsf", tgsf_text_backend(), be);
+    tgsf_text* tx = new tgsf_text;
+    tx->device = device;
+    tx->max_bytes = max_bytes;
+    tx->max_records = max_records;
+    tx->max_pieces = (max_bytes + kTextPiece - 1) / kTextPiece;
+    tx->stream = nullptr;
+#if !defined(TGSF_EMUL)
+    if (hipSetDevice(device) != hipSuccess) { delete tx; return fail(nullptr, TGSF_E_NO_DEVICE, "hipSetDevice(%d) failed: no usable HIP device (there is no CPU fallback)", device); }
+    if (hipStreamCreateWithFlags(&tx->stream, hipStreamNonBlocking) != hipSuccess) { delete tx; return fail(nullptr, TGSF_E_HIP, "stream creation failed"); }
+    for (hipEvent_t& e : tx->ev) if (hipEventCreate(&e) != hipSuccess) { tgsf_text_destroy(tx); return fail(nullptr, TGSF_E_HIP, "event creation failed"); }
+#endif
+    const uint64_t text_bytes = ((max_bytes + 15u) & ~15ull) + TGSF_TEXT_PAD;
+    int e = 0;
+    e |= dev_alloc(tx, &tx->d_text, text_bytes);
+    if (!e) e |= dev_alloc(tx, &tx->d_bits, tx->max_pieces * kTextPieceWords);
+    if (!e) e |= dev_alloc(tx, &tx->d_cnt, tx->max_pieces + 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_part, tx->max_pieces / kTextScanTile + 2);
+    if (!e) e |= dev_alloc(tx, &tx->d_table, 4ull * max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_state, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_index.seq_off, max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_index.qual_off, max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_index.len, max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_index.name_off, max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_index.name_len, max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_summary, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_reads, max_records);
+    if (!e) e |= dev_alloc(tx, &tx->d_nfrags, 4);
+    if (e) {
+        tgsf_text_destroy(tx);
+        return fail(nullptr, TGSF_E_HIP, "device allocation failed (%llu bytes of text, %u records)", (unsigned long long)max_bytes, max_records);
+    }
+    *out = tx;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_profile(tgsf_text* tx, int enable)
+{
+    if (!tx) return TGSF_E_INVALID;
+    tx->profile = enable != 0;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_buffers(tgsf_text* tx, tgsf_text_device_buffers* out)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!out) return fail(tx, TGSF_E_INVALID, "null argument");
+    out->text = tx->d_text;
+    out->index = tx->d_index;
+    out->summary = tx->d_summary;
+    out->max_bytes = tx->max_bytes;
+    out->max_records = tx->max_records;
+    out->reserved = 0;
+    return TGSF_OK;
+}
+
+static unsigned blocks_for(uint64_t items, unsigned per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+
+// the seven launches of one index, on st; nothing is waited for
+static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int fasta, int final,
+                         const tgsf_text_index_arrays& I, tgsf_text_summary* d_summary, rt_stream st)
+{
+    const uint64_t pieces = (n + kTextPiece - 1) / kTextPiece;
+    const uint32_t nb = (uint32_t)((pieces + kTextScanTile - 1) / kTextScanTile);
+    const uint64_t cap = (fasta ? 2ull : 4ull) * tx->max_records;
+    const unsigned gwave = blocks_for(pieces * kTextLanes, kTextThreads);          // a wave per piece
+    const unsigned gemit = blocks_for((pieces + kTextEmitPieces - 1) / kTextEmitPieces * kTextLanes, kTextThreads);
+    const unsigned gsmall = grid_cap(std::min(blocks_for(tx->max_records, kTextThreads), 2048u));
+    const unsigned gfold = std::min(gsmall, 64u);                                  // every wave ends in two atomics on one word each
+#if !defined(TGSF_EMUL)
+    if (tx->profile) { (void)hipEventRecord(tx->ev[0], st); }
+#endif
+    if (pieces) {
+        TGSF_LAUNCH(k_text_mark, gwave, kTextThreads, st, d_text, n, pieces, (uint16_t*)tx->d_bits, tx->d_cnt);
+        TGSF_LAUNCH_COOP(k_text_scan_tiles, nb, 256, st, tx->d_cnt, pieces, tx->d_part);
+    }
+    TGSF_LAUNCH_COOP(k_text_scan_top, 1, 64, st, tx->d_part, nb, tx->d_state);
+    if (pieces)
+        TGSF_LAUNCH(k_text_emit, gemit, kTextThreads, st, (const uint64_t*)tx->d_bits, (const uint32_t*)tx->d_cnt,
+                    (const uint64_t*)tx->d_part, pieces, tx->d_table, cap);
+    TGSF_LAUNCH(k_text_check, gsmall, kTextThreads, st, d_text, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, tx->d_state, I);
+    TGSF_LAUNCH(k_text_fold, gfold, kTextThreads, st, (const uint32_t*)I.len, fasta, tx->max_records, tx->d_state);
+    TGSF_LAUNCH_COOP(k_text_finish, 1, 64, st, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, (const TextState*)tx->d_state, d_summary);
+#if !defined(TGSF_EMUL)
+    if (tx->profile) { (void)hipEventRecord(tx->ev[1], st); tx->ev_recorded = true; }
+    if (hipGetLastError() != hipSuccess) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+#endif
+    return TGSF_OK;
+}
+
+// milliseconds between the events around the last index; the stream has been synchronised
+static float index_ms(tgsf_text* tx)
+{
+#if !defined(TGSF_EMUL)
+    float ms = 0.0f;
+    if (tx->profile && tx->ev_recorded && hipEventElapsedTime(&ms, tx->ev[0], tx->ev[1]) == hipSuccess) { tx->ev_recorded = false; return ms; }
+    (void)hipGetLastError();
+#endif
+    (void)tx;
+    return 0.0f;
+}
+
+static int check_args(tgsf_text* tx, uint64_t n_bytes, int fasta, int final)
+{
+    if ((fasta != 0 && fasta != 1) || (final != 0 && final != 1)) return fail(tx, TGSF_E_INVALID, "fasta and final are 0 or 1");
+    if (n_bytes > tx->max_bytes)
+        return fail(tx, TGSF_E_CAPACITY, "text of %llu bytes, the indexer was created for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_bytes);
+    return TGSF_OK;
+}
+
+static int upload(tgsf_text* tx, const uint8_t* text, uint64_t n_bytes)
+{
+    int he = 0;
+    if (n_bytes) he |= rt_h2d(tx->d_text, text, n_bytes, tx->stream);
+    he |= rt_memset(tx->d_text + n_bytes, 0, (size_t)((((n_bytes + 15u) & ~15ull) - n_bytes) + TGSF_TEXT_PAD), tx->stream);
+    return he ? fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he)) : TGSF_OK;
+}
+
+extern "C" int tgsf_text_upload(tgsf_text* tx, const uint8_t* text, uint64_t n_bytes)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!text && n_bytes) return fail(tx, TGSF_E_INVALID, "null text");
+    if (n_bytes > tx->max_bytes)
+        return fail(tx, TGSF_E_CAPACITY, "text of %llu bytes, the indexer was created for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_bytes);
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    int e = upload(tx, text, n_bytes);
+    if (e) return e;
+    const int he = rt_sync(tx->stream);
+    return he ? fail(tx, TGSF_E_HIP, "stream synchronize failed: %s", rt_errstr(he)) : TGSF_OK;
+}
+
+extern "C" int tgsf_text_index_device(tgsf_text* tx, const uint8_t* d_text, uint64_t n_bytes, int fasta, int final,
+                                      const tgsf_text_index_arrays* d_index, tgsf_text_summary* d_summary, void* hip_stream)
+{
+    if (!tx) return TGSF_E_INVALID;
+    int e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+    if (!d_text) d_text = tx->d_text;
+    if ((uintptr_t)d_text & 15u) return fail(tx, TGSF_E_INVALID, "the device text must be 16-byte aligned");
+    if (d_index && (!d_index->seq_off || !d_index->qual_off || !d_index->len || !d_index->name_off || !d_index->name_len))
+        return fail(tx, TGSF_E_INVALID, "a device index needs all five arrays");
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    return enqueue_index(tx, d_text, n_bytes, fasta, final, d_index ? *d_index : tx->d_index, d_summary ? d_summary : tx->d_summary,
+                         hip_stream ? (rt_stream)hip_stream : tx->stream);
+}
+
+// the object's own summary and index to the host; the copies run on the object's stream, which is waited for
+static int fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_text_summary* sum)
+{
+    int he = rt_d2h(sum, tx->d_summary, sizeof *sum, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    sum->device_ms = index_ms(tx);
+    const size_t k = sum->n_records;
+    if (out_index && k) {
+        if (out_index->seq_off) he |= rt_d2h(out_index->seq_off, tx->d_index.seq_off, k * 8, tx->stream);
+        if (out_index->qual_off) he |= rt_d2h(out_index->qual_off, tx->d_index.qual_off, k * 8, tx->stream);
+        if (out_index->len) he |= rt_d2h(out_index->len, tx->d_index.len, k * 4, tx->stream);
+        if (out_index->name_off) he |= rt_d2h(out_index->name_off, tx->d_index.name_off, k * 8, tx->stream);
+        if (out_index->name_len) he |= rt_d2h(out_index->name_len, tx->d_index.name_len, k * 4, tx->stream);
+        if (!he) he = rt_sync(tx->stream);
+        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    }
+    if (out_summary) *out_summary = *sum;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    tgsf_text_summary sum;
+    return fetch(tx, out_index, out_summary, &sum);
+}
+
+extern "C" int tgsf_text_index(tgsf_text* tx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
+                               const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!out_summary || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    if ((e = upload(tx, text, n_bytes))) return e;
+    if ((e = enqueue_index(tx, tx->d_text, n_bytes, fasta, final, tx->d_index, tx->d_summary, tx->stream))) return e;
+    tgsf_text_summary sum;
+    return fetch(tx, out_index, out_summary, &sum);
+}
+
+extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
+                                const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    if (bo->frags && bo->frag_capacity > tx->frag_cap) {               // fragment records on the device: as many as the caller takes
+        tgsf_fragment* f = nullptr;
+        if (dev_alloc(tx, &f, bo->frag_capacity)) return fail(tx, TGSF_E_HIP, "device allocation failed (%u fragment records)", bo->frag_capacity);
+        tx->d_frags = f;                                               // (the smaller one stays allocated until destroy)
+        tx->frag_cap = bo->frag_capacity;
+    }
+    if ((e = upload(tx, text, n_bytes))) return e;
+    if ((e = enqueue_index(tx, tx->d_text, n_bytes, fasta, final, tx->d_index, tx->d_summary, tx->stream))) return e;
+    tgsf_text_summary sum;
+    // the one wait between the index and the filter: libtgsf sizes its launches by n_reads on the host
+    if ((e = fetch(tx, nullptr, nullptr, &sum))) return e;
+    bo->n_frags = 0;
+    if (sum.n_records) {
+        tgsf_batch_in in;
+        memset(&in, 0, sizeof in);
+        in.seq = tx->d_text;
+        in.qual = tx->d_text;
+        in.offsets = tx->d_index.seq_off;
+        in.lengths = tx->d_index.len;
+        in.qual_offsets = tx->d_index.qual_off;
+        in.n_reads = sum.n_records;
+        in.n_bytes = n_bytes;
+        tgsf_batch_out dout;
+        dout.reads = tx->d_reads;
+        dout.frags = bo->frags ? tx->d_frags : nullptr;
+        dout.frag_capacity = bo->frags ? bo->frag_capacity : 0u;
+        dout.n_frags = 0;
+        e = tgsf_submit_device(ctx, &in, &dout, tx->d_nfrags, (void*)tx->stream);
+        if (!e) e = tgsf_wait(ctx);
+        if (e) return fail(tx, e, "libtgsf: %s", tgsf_last_error(ctx));
+        uint32_t nf = 0;
+        int he = rt_d2h(&nf, tx->d_nfrags, 4, tx->stream);
+        he |= rt_d2h(bo->reads, tx->d_reads, (size_t)sum.n_records * sizeof(tgsf_read_result), tx->stream);
+        if (!he) he = rt_sync(tx->stream);
+        if (!he && nf > dout.frag_capacity) return fail(tx, TGSF_E_CAPACITY, "batch produced %u fragments, caller provided room for %u", nf, dout.frag_capacity);
+        if (!he && nf) {
+            he = rt_d2h(bo->frags, tx->d_frags, (size_t)nf * sizeof(tgsf_fragment), tx->stream);
+            if (!he) he = rt_sync(tx->stream);
+        }
+        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+        bo->n_frags = nf;
+    }
+    // the index last: the filter does not wait for it
+    tgsf_text_summary again;
+    if (out_index && (e = fetch(tx, out_index, nullptr, &again))) return e;
+    *out_summary = sum;
+    return TGSF_OK;
+}

@@ -1,0 +1,187 @@
+"""ctypes binding of libtgsf_text.so (include/tgsf_text.h): the record index of FASTQ / FASTA text, made on the GPU.
+
+    tx = TextIndexer(0, max_bytes=len(text), max_records=100_000)
+    idx, summary = tx.index(text)                       # five numpy arrays + the summary
+    idx, summary, reads, frags = tx.submit(ctx, text)   # text in, filter results out (ctx: capi.Context)
+
+There is no CPU fallback: the library found beside this file must be the HIP build.  (tests/emul builds a serial
+emulation of the same kernels; only tests pass its path in.)
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+from collections import namedtuple
+
+import numpy as np
+
+from . import abi
+from .capi import TgsfError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+DEFAULT_LIB = os.path.join(_HERE, "libtgsf_text.so")
+_LIBS = {}
+
+ABI_VERSION = 1
+END, IRREGULAR, CAPACITY = 0, 1, 2
+STOP_NAMES = {END: "END", IRREGULAR: "IRREGULAR", CAPACITY: "CAPACITY"}
+PAD = 64
+
+SYMBOLS = [
+    "tgsf_text_abi_version", "tgsf_text_backend", "tgsf_text_create", "tgsf_text_destroy", "tgsf_text_last_error", "tgsf_text_profile",
+    "tgsf_text_buffers", "tgsf_text_index", "tgsf_text_upload", "tgsf_text_index_device", "tgsf_text_fetch", "tgsf_text_submit",
+]
+
+
+class Summary(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("stop", C.c_uint32), ("consumed", C.c_uint64), ("bases", C.c_uint64),
+                ("longest", C.c_uint32), ("device_ms", C.c_float)]
+
+    def as_dict(self):
+        return {"n_records": self.n_records, "stop": self.stop, "consumed": self.consumed, "bases": self.bases,
+                "longest": self.longest, "device_ms": self.device_ms}
+
+
+class IndexArrays(C.Structure):
+    _fields_ = [("seq_off", C.c_void_p), ("qual_off", C.c_void_p), ("len", C.c_void_p), ("name_off", C.c_void_p), ("name_len", C.c_void_p)]
+
+
+class DeviceBuffers(C.Structure):
+    _fields_ = [("text", C.c_void_p), ("index", IndexArrays), ("summary", C.c_void_p), ("max_bytes", C.c_uint64),
+                ("max_records", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(Summary) == 32
+
+Index = namedtuple("Index", "seq_off qual_off len name_off name_len")
+
+
+def load(path: str | None = None):
+    """`path` if given (the tests hand the emulation's in), else the in-tree HIP build, which must answer "hip..."."""
+    explicit = path is not None
+    path = path or DEFAULT_LIB
+    if path not in _LIBS:
+        if not os.path.exists(path):
+            raise FileNotFoundError(
+                f"{path} not found: build the HIP extension first (python -c 'import __graft_entry__ as g; g.build()')")
+        L = C.CDLL(path)
+        vp, u64, i = C.c_void_p, C.c_uint64, C.c_int
+        L.tgsf_text_abi_version.restype = i
+        L.tgsf_text_backend.restype = C.c_char_p
+        L.tgsf_text_create.argtypes = [i, u64, C.c_uint32, C.POINTER(vp)]
+        L.tgsf_text_destroy.argtypes = [vp]
+        L.tgsf_text_destroy.restype = None
+        L.tgsf_text_last_error.argtypes = [vp]
+        L.tgsf_text_last_error.restype = C.c_char_p
+        L.tgsf_text_profile.argtypes = [vp, i]
+        L.tgsf_text_buffers.argtypes = [vp, C.POINTER(DeviceBuffers)]
+        L.tgsf_text_index.argtypes = [vp, vp, u64, i, i, C.POINTER(IndexArrays), C.POINTER(Summary)]
+        L.tgsf_text_upload.argtypes = [vp, vp, u64]
+        L.tgsf_text_index_device.argtypes = [vp, vp, u64, i, i, C.POINTER(IndexArrays), vp, vp]
+        L.tgsf_text_fetch.argtypes = [vp, C.POINTER(IndexArrays), C.POINTER(Summary)]
+        L.tgsf_text_submit.argtypes = [vp, vp, vp, u64, i, i, C.POINTER(IndexArrays), C.POINTER(Summary), C.POINTER(abi.BatchOut)]
+        if L.tgsf_text_abi_version() != ABI_VERSION:
+            raise RuntimeError("libtgsf_text ABI version mismatch")
+        _LIBS[path] = L
+    L = _LIBS[path]
+    if not explicit and not L.tgsf_text_backend().startswith(b"hip"):
+        raise RuntimeError(f"{path} is the {L.tgsf_text_backend().decode()!r} build of libtgsf_text, not the HIP build (there is no CPU fallback)")
+    return L
+
+
+def _as_u8(text):
+    if isinstance(text, (bytes, bytearray, memoryview)):
+        return np.frombuffer(text, dtype=np.uint8)
+    return np.ascontiguousarray(text, dtype=np.uint8)
+
+
+class TextIndexer:
+    """One tgsf_text object: device buffers for chunks of up to max_bytes bytes and max_records records, and a stream."""
+
+    def __init__(self, device: int, max_bytes: int, max_records: int, lib_path: str | None = None):
+        self.lib = load(lib_path)
+        self.max_bytes, self.max_records = int(max_bytes), int(max_records)
+        h = C.c_void_p()
+        rc = self.lib.tgsf_text_create(device, self.max_bytes, self.max_records, C.byref(h))
+        if rc != 0:
+            raise TgsfError(rc, self.lib.tgsf_text_last_error(None).decode())
+        self.h = h
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.tgsf_text_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def profile(self, enable=True):
+        self._chk(self.lib.tgsf_text_profile(self.h, int(enable)))
+
+    def buffers(self) -> DeviceBuffers:
+        """Device addresses of the object's text buffer, index arrays and summary."""
+        b = DeviceBuffers()
+        self._chk(self.lib.tgsf_text_buffers(self.h, C.byref(b)))
+        return b
+
+    def _host_index(self):
+        m = self.max_records
+        arrs = Index(np.zeros(m, np.uint64), np.zeros(m, np.uint64), np.zeros(m, np.uint32), np.zeros(m, np.uint64), np.zeros(m, np.uint32))
+        return arrs, IndexArrays(*[a.ctypes.data for a in arrs])
+
+    @staticmethod
+    def _clip(arrs, n):
+        return Index(*[a[:n].copy() for a in arrs])
+
+    def index(self, text, fasta=False, final=True):
+        """Index a chunk held in host memory: (Index of n_records entries each, summary dict)."""
+        t = _as_u8(text)
+        arrs, ia = self._host_index()
+        s = Summary()
+        self._chk(self.lib.tgsf_text_index(self.h, t.ctypes.data, t.size, int(fasta), int(final), C.byref(ia), C.byref(s)))
+        return self._clip(arrs, s.n_records), s.as_dict()
+
+    def upload(self, text):
+        """The text into the object's device buffer (zero-padded), nothing else."""
+        t = _as_u8(text)
+        self._chk(self.lib.tgsf_text_upload(self.h, t.ctypes.data, t.size))
+        return t.size
+
+    def index_device(self, n_bytes, fasta=False, final=True, d_text=None, d_index: IndexArrays | None = None, d_summary=None, stream=None):
+        """Enqueue the index of text already in HBM (d_text None: the object's buffer, see upload) without waiting.
+        d_index None: the index stays in the object's arrays (buffers().index); fetch() brings it to the host."""
+        self._chk(self.lib.tgsf_text_index_device(self.h, d_text, int(n_bytes), int(fasta), int(final),
+                                                  C.byref(d_index) if d_index is not None else None, d_summary, stream))
+
+    def fetch(self, want_index=True):
+        """Wait for the object's stream; the object's own index and summary as index() returns them."""
+        s = Summary()
+        if not want_index:
+            self._chk(self.lib.tgsf_text_fetch(self.h, None, C.byref(s)))
+            return None, s.as_dict()
+        arrs, ia = self._host_index()
+        self._chk(self.lib.tgsf_text_fetch(self.h, C.byref(ia), C.byref(s)))
+        return self._clip(arrs, s.n_records), s.as_dict()
+
+    def submit(self, ctx, text, fasta=False, final=True, frag_capacity=None, want_index=True):
+        """Text in, filter results out: (Index or None, summary dict, reads, frags) for the regular prefix of `text`,
+        through `ctx` (a capi.Context of the same device and the same build; no_qual for FASTA)."""
+        t = _as_u8(text)
+        if frag_capacity is None:
+            frag_capacity = t.size // 100 + self.max_records + 16
+        arrs, ia = self._host_index() if want_index else (None, None)
+        reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
+        frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
+        bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
+        s = Summary()
+        self._chk(self.lib.tgsf_text_submit(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final),
+                                            C.byref(ia) if want_index else None, C.byref(s), C.byref(bo)))
+        n = s.n_records
+        return (self._clip(arrs, n) if want_index else None), s.as_dict(), reads[:n].copy(), frags[:bo.n_frags].copy()
