@@ -4,6 +4,7 @@
 //   Output               single-stream writer: records gathered with writev straight from the input text, or per-record
 //                        gzip members (the reference's writer, src/TGSFilter.cpp:2095-2145, :786-812)
 //   MappedSink + Pool    plain output into a regular file from several threads (phased fallocate + mapped fill)
+//   MappedWriter         ... and what either pass puts around them: reserver, populate and fill pools, releaser
 #pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -41,6 +42,16 @@
 
 namespace host {
 
+// a record to write: a kept fragment, addressed in the input text (record_out.h has its layout; a downsampling run keeps
+// these of the whole filter pass in memory)
+struct CleanRec {
+    std::string_view name;
+    int pass_num;
+    const char* seq;
+    const char* qual;
+    uint32_t len;
+};
+
 // A batch is a slice [base, base+span) of the input text plus an index of its records: nothing is
 // copied on the host; the library reads sequence and quality lines in place (tgsf_batch_in.qual_offsets).
 struct Batch {
@@ -54,7 +65,7 @@ struct Batch {
     uint32_t n_frags = 0;
     uint64_t bases = 0;
     uint64_t id = 0;                         // position in the input: the writer puts batches back in order
-    struct Emit { uint32_t read, frag; int pass_num; uint64_t at; };   // a record to write, `at` bytes into the batch's output
+    struct Emit { CleanRec rec; uint64_t at; };   // a record to write, `at` bytes into the batch's output
     std::vector<Emit> em;
     std::shared_ptr<Chunk> hold;             // streamed input: the chunk of text this batch's records live in
     char* dst = nullptr;                     // where the batch's output starts in the mapped file
@@ -88,15 +99,6 @@ public:
 private:
     std::mutex m_;
     std::vector<std::shared_ptr<Batch>> free_;
-};
-
-// a kept fragment, addressed in the input text (used when a downsampling pass follows the filter pass)
-struct CleanRec {
-    std::string_view name;
-    int pass_num;
-    const char* seq;
-    const char* qual;
-    uint32_t len;
 };
 
 template <class T>
@@ -493,13 +495,13 @@ private:
 
 // The output file's pages, made ready ahead of the planner by a thread of its own.  A stride of the file is instantiated
 // (fallocate: one thread, 13-16 GB/s, the critical path of a run that writes a tmpfs file) and then its pages are mapped
-// (MADV_POPULATE_WRITE on the populate pool) -- either between two fallocates (page faults on a file take its inode's
-// i_lock while a fallocate is in progress on it, shmem_falloc_wait: dozens of faulting threads beside a fallocate drag
-// both down), or, `beside` > 0, by a FEW threads while the next stride is being instantiated.  The planner says how far
-// the file will probably go (want) and waits for the part it is about to hand to the fill threads (wait_ready).
+// (MADV_POPULATE_WRITE on the populate pool) between two fallocates (page faults on a file take its inode's i_lock while a
+// fallocate is in progress on it, shmem_falloc_wait: dozens of faulting threads beside a fallocate drag both down).  The
+// planner says how far the file will probably go (want) and waits for the part it is about to hand to the fill threads
+// (wait_ready).
 class Reserver {
 public:
-    Reserver(MappedSink& sink, Pool& populate, uint64_t stride, bool beside) : sink_(sink), pop_(populate), stride_(stride), beside_(beside) {}
+    Reserver(MappedSink& sink, Pool& populate, uint64_t stride) : sink_(sink), pop_(populate), stride_(stride) {}
     ~Reserver() { finish(); }
     // speculative: up to `limit` while nothing else is known (a failure just ends the speculation)
     void start(uint64_t speculative_limit) {
@@ -522,7 +524,7 @@ public:
         cv_.notify_all();
         if (th_.joinable()) th_.join();
     }
-    double t_populate_wait = 0;                 // fallocate waiting for the mapping of the stride before (serial mode)
+    double t_populate_wait = 0;                 // fallocate waiting for the mapping of the stride before
 private:
     void piece_done(size_t k) {
         std::lock_guard<std::mutex> l(m_);
@@ -556,14 +558,14 @@ private:
                 { std::lock_guard<std::mutex> l(m_); k = done_.size(); done_.push_back(0); ends_.push_back(o + n); }
                 pop_.add([this, o, n, k] { sink_.populate(o, n); piece_done(k); });
             }
-            if (!beside_) { pop_.drain(); t_populate_wait += now_s() - d0; }
+            pop_.drain();
+            t_populate_wait += now_s() - d0;
             at = upto;
         }
     }
     MappedSink& sink_;
     Pool& pop_;
     const uint64_t stride_;
-    const bool beside_;
     std::mutex m_;
     std::condition_variable cv_, ready_cv_;
     uint64_t goal_ = 0, need_ = 0, ready_ = 0;
@@ -574,6 +576,78 @@ private:
     std::thread th_;
 };
 
-
+// A mapped output file and the threads around it, for either pass: the sink, the reserver with its populate pool ahead of the
+// planner, the fill pool behind it, and the one thread that drops the mappings of what was written.  The planner's protocol:
+// claim the next bytes of the file (they are instantiated and mapped when claim returns), hand fill jobs for them to the pool,
+// which say release when they are done; finish when the last job is handed over.
+class MappedWriter {
+public:
+    MappedSink sink;
+    bool is_open() const { return sink.is_open(); }
+    bool open(const std::string& path, uint64_t capacity, bool only_new = false) { return sink.open(path, capacity, only_new); }
+    // before anything else of the run is known (the library still loads, no pool exists): pages are instantiated up to
+    // `limit` by a bare thread, and mapped by the reserver's first round
+    void reserve_early(uint64_t limit) {
+        early_ = std::thread([this, limit] {
+            CpuScope cpu(CPU_FALLOCATE);
+            while (!early_stop_.load() && sink.reserved() < limit)
+                if (!sink.reserve_to(std::min<uint64_t>(limit, sink.reserved() + (256u << 20)), false)) break;   // (a nearly full file system: not this thread's call)
+        });
+    }
+    // the reserver: strides of `stride` bytes, mapped by `populate_threads`; up to `speculative` before the first claim
+    void start_reserving(int populate_threads, uint64_t stride, uint64_t speculative) {
+        if (early_.joinable()) { early_stop_ = true; early_.join(); }
+        populate_.reset(new Pool(is_open() ? populate_threads : 0, CPU_POPULATE));
+        reserver_.reset(new Reserver(sink, *populate_, stride));
+        if (is_open()) reserver_->start(speculative);
+    }
+    // the fill pool, and the releaser: mappings are dropped in pieces of `release_piece` bytes by ONE background thread (from
+    // the 16 fill threads at once that cost 7-15 thread-seconds of a run and slowed everything beside them)
+    void start_filling(int fill_threads, uint64_t release_piece) {
+        pool_.reset(new Pool(is_open() ? fill_threads : 1));
+        releaser_ = std::thread([this, release_piece] {
+            CpuScope cpu(CPU_RELEASER);
+            for (;;) {
+                const std::pair<const char*, uint64_t> r = to_release_.get();
+                if (!r.first) break;
+                for (uint64_t o = 0; o < r.second; o += release_piece) MappedSink::release(r.first + o, std::min<uint64_t>(release_piece, r.second - o));
+            }
+        });
+    }
+    // the next n bytes of the file, instantiated AND mapped (the fill jobs take no fault); the file will probably reach `estimate`
+    char* claim(uint64_t n, uint64_t estimate) {
+        const uint64_t end = sink.planned() + n;
+        if (end > sink.capacity()) die("output more than four times the size of the input: larger than the space mapped for it (TGSF_WRITER=writev writes such a file)");
+        reserver_->want(std::min<uint64_t>(std::max<uint64_t>(estimate, end), sink.capacity()), end);
+        const double d0 = now_s();
+        reserver_->wait_ready(end);
+        t_claim_wait += now_s() - d0;
+        return sink.place(n);
+    }
+    void fill(std::function<void()> job) { pool_->add(std::move(job)); }
+    // [p, p+n) is written (or, a piece of the input text, read): its mapping can go
+    void release(const char* p, uint64_t n) { to_release_.put({p, n}); }
+    void finish() {
+        reserver_->finish();
+        t_planned = now_s();
+        pool_->finish();
+        populate_->finish();
+        to_release_.put({nullptr, 0});
+        releaser_.join();
+        t_fill_tail = now_s() - t_planned;
+        sink.close();
+        t_close = now_s() - t_planned - t_fill_tail;
+    }
+    Pool& pool() { return *pool_; }
+    double t_populate_wait() const { return reserver_->t_populate_wait; }
+    double t_claim_wait = 0;                    // the planner waiting for pages of the file
+    double t_planned = 0, t_fill_tail = 0, t_close = 0;   // finish: when it began, the last fill jobs and releases, closing the file
+private:
+    std::atomic<bool> early_stop_{false};
+    std::thread early_, releaser_;
+    std::unique_ptr<Pool> populate_, pool_;
+    std::unique_ptr<Reserver> reserver_;
+    Channel<std::pair<const char*, uint64_t>> to_release_{1 << 16};
+};
 
 }  // namespace host

@@ -8,6 +8,7 @@
 //   make_contexts       batch sizes, output sink, library joined, RCCL communicator started, tgsf_params
 //   filter_pass         indexer -> batcher -> feeders (tgsf_submit) -> ordered planner -> fill threads             run_pipeline.cpp, run_writer.cpp
 //   downsample          DownSampleTask (:2164-2568): selection over all ranks' fragments, QC pass, writing        run_downsample.cpp, run_second_pass.cpp
+//                       (a record's layout: record_out.h; the mapped output of either pass: MappedWriter, pipeline.h)
 //   sum_tallies         contexts -> ranks (RCCL all-reduce, checked against the sum over the sockets) -> rank 0   run_report.cpp
 //   report              statistics, INFO lines, HTML report (:3146-3328); stale part files of earlier jobs
 //   timing_lines        TGSF_TIMING's lines
@@ -53,7 +54,7 @@ struct Run {
     bool sharded = false;               // --ranks / --shard (also with one rank: the same program path, one part file)
     bool timing = false;                // TGSF_TIMING: stage wall times on stderr (not part of the surface)
     double t_epoch0 = 0, t_start = 0;
-    double t_drain = 0, t_prepass = 0, t_pipe = 0, t_parse = 0, t_gpu = 0, t_write = 0, t_widle = 0, t_first = 0;
+    double t_prepass = 0, t_pipe = 0, t_parse = 0, t_gpu = 0, t_write = 0, t_widle = 0, t_first = 0;
 
     // ---- input ----
     std::string html;
@@ -69,11 +70,9 @@ struct Run {
 
     // ---- output ----
     std::string out_path;
-    MappedSink sink;
-    std::atomic<bool> early_stop{false};
-    std::thread early;
-    void end_early() { if (early.joinable()) { early_stop = true; early.join(); } }
-    Output out;
+    bool plain_file_out() const;        // plain output into a named file, not forced to the single-stream writer: a MappedWriter may take it
+    MappedWriter mapped;                // the filter pass's output, where it is written through a mapping ...
+    Output out;                         // ... and every other kind of output, of either pass
     bool fastq_out = false, run_filter_pass = true;
 
     // ---- pre-pass ----
@@ -112,12 +111,8 @@ struct Run {
     std::vector<uint64_t> dev_bytes, dev_batches;
     int fill_threads = 1, populate_threads = 1;
     uint64_t fill_min = 1u << 20, stride_bytes = 2ull << 30;
-    std::unique_ptr<Pool> pool, populate;
-    std::unique_ptr<Reserver> reserver;
     bool release_input = false, release_output = false;
-    std::unique_ptr<Channel<std::pair<const char*, uint64_t>>> to_release;
     bool mapped_out = false;
-    double t_f0 = 0, t_busy = 0, t_fill_tail = 0, t_close = 0;
     void reader_body();
     void feed(size_t k);
     void bind_to_node_of(size_t k);
@@ -126,10 +121,8 @@ struct Run {
     void batch_done(std::shared_ptr<Batch> b);
 
     // ---- downsampling ----
-    std::unique_ptr<MappedSink> dsink;
-    std::unique_ptr<Pool> dpop;
-    std::unique_ptr<Reserver> dres;
-    bool open_dsink(uint64_t capacity, uint64_t speculative);
+    MappedWriter down_mapped;           // the selection's output, where it is written through a mapping
+    bool open_down_mapped(uint64_t capacity, uint64_t speculative);
     uint64_t down_bases = 0, down_job_recs = 0, down_job_bases = 0;
     std::vector<int> down_lens;
     std::vector<uint64_t> down_t;
@@ -138,6 +131,11 @@ struct Run {
     bool d_in_place = false, d_mapped = false;
     std::vector<char> select_kept();    // the reference's selection (:2297-2344), over all ranks' fragments: keep flag per clean_recs entry
     void second_pass(const std::vector<char>& keep);
+    std::thread start_qc_feed(const std::vector<char>& keep, tgsf_ctx*& qctx, tgsf_ctx*& qctx2);   // the kept records through the QC tallies ...
+    void feed_in_place(const std::vector<uint32_t>& by_addr, const tgsf_params& qp, uint64_t kept_span, tgsf_ctx* qctx, tgsf_ctx*& qctx2);
+    void feed_packed(const std::vector<char>& keep, const tgsf_params& qp, size_t room, tgsf_ctx* qctx);
+    void write_kept(const std::vector<char>& keep);                                                // ... written beside that ...
+    void merge_down_tallies(tgsf_ctx* qctx, tgsf_ctx* qctx2);                                      // ... and the tallies of feeders and ranks summed
 
     // ---- tallies, report ----
     uint64_t nw = 0;
@@ -152,6 +150,7 @@ struct Run {
 
 // A rank's tally vector as it travels to rank 0 over the sockets: everything in front of the four per-100-bp tables, then of
 // each of those only the rows in use; and its sum into rank 0's vector (the four "rows used" words are maxima).
+void add_tallies(std::vector<uint64_t>& v, const std::vector<uint64_t>& part, int32_t bc, uint32_t nbins);   // a whole vector into another
 std::vector<uint64_t> pack_rows(const std::vector<uint64_t>& v, int32_t bc, uint32_t nbins);
 void add_rows(std::vector<uint64_t>& v, const std::vector<uint64_t>& ru, int32_t bc, uint32_t nbins);
 

@@ -118,17 +118,15 @@ void Run::make_contexts()
     fastq_out = o.out_type == 1;
     run_filter_pass = o.filter || o.only_qc;                // :3061; with -F the input goes straight to downsampling
     {
-        const char* w = getenv("TGSF_WRITER");                         // "writev": always the single-stream writer
-        const bool may_map = !o.only_qc && !o.out_gz && !o.downsample && run_filter_pass && !o.out_file.empty() &&
-                             !(w && !strcmp(w, "writev"));
+        const bool may_map = plain_file_out() && !o.only_qc && !o.downsample && run_filter_pass;
         // address space for the output mapping: what the input could turn into (a streamed input's text size is unknown)
         // (address space only: pages exist where records are laid out.  A record's header is repeated in front of each of
         // its fragments, so an output can outgrow its input -- by a factor only headers of kilobytes reach.)
-        if (may_map && !sink.is_open()) sink.open(out_path, streaming ? std::max<uint64_t>(64ull << 30, 64ull * in.size())
+        if (may_map && !mapped.is_open()) mapped.open(out_path, streaming ? std::max<uint64_t>(64ull << 30, 64ull * in.size())
                                                                       : 4 * (uint64_t)text_size + (1ull << 30));
         Options oo = o;
         oo.out_file = out_path;
-        if (!o.only_qc && !sink.is_open() && !out.open(oo)) leave(1);
+        if (!o.only_qc && !mapped.is_open() && !out.open(oo)) leave(1);
     }
     api = &lib();
     const Api& L = *api;                                              // joins the loader thread

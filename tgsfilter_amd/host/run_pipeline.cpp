@@ -157,12 +157,12 @@ void Run::feed(size_t k)
     to_writer->put(nullptr);
 }
 
-// a written batch: its mappings go to the releaser thread where they are dropped at all (from the 16 fill threads at once
-// that cost 7-15 thread-seconds of a run and slowed everything beside them), the batch itself back to the store
+// a written batch: its mappings go to the releaser thread where they are dropped at all (MappedWriter), the batch itself back
+// to the store
 void Run::batch_done(std::shared_ptr<Batch> b)
 {
-    if (b->out_bytes && release_output) to_release->put({b->dst, b->out_bytes});
-    if (release_input) to_release->put({b->base, b->span});
+    if (b->out_bytes && release_output) mapped.release(b->dst, b->out_bytes);
+    if (release_input) mapped.release(b->base, b->span);
     store.put(std::move(b));
 }
 
@@ -198,28 +198,21 @@ void Run::filter_pass()
     fill_threads = std::max(1, std::min(o.n_thread, 16));
     fill_min = 1u << 20;                                      // bytes worth a job of their own
     if (const char* e = knob("TGSF_FILL_MIN_BYTES")) { const long long v = atoll(e); if (v > 0) fill_min = (uint64_t)v; }   // test knob
-    pool.reset(new Pool(sink.is_open() ? fill_threads : 1));
     populate_threads = std::max(1, std::min(o.n_thread, 32));      // short bursts between two fallocates: the more the shorter
     if (const char* e = knob("TGSF_POPULATE_THREADS")) { const int v = atoi(e); if (v >= 1 && v <= 64) populate_threads = v; }   // tuning knob (tests/manual/e2e_cpu.py)
-    // (the pages of a reserved stride are mapped by many threads BETWEEN two fallocates: beside one, page faults on the file
-    // take its inode's lock and both crawl -- measured, DESIGN appendix)
-    populate.reset(new Pool(sink.is_open() ? populate_threads : 0, CPU_POPULATE));
     // (a streamed input is decoder-bound: small strides keep the mapped part of the output -- it counts as resident -- small)
     stride_bytes = streaming ? (128ull << 20) : (2ull << 30);
     if (const char* e = knob("TGSF_STRIDE_BYTES")) { const long long v = atoll(e); if (v > 0) stride_bytes = (uint64_t)v; }   // tuning / test knob
     // While the library loads and the device comes up pages of the output file are instantiated already, up to a quarter
     // of the input's size (what a run keeps is not known yet; a surplus is cut off at the end).
-    end_early();                                                       // (what it reserved is mapped by the reserver's first round)
-    reserver.reset(new Reserver(sink, *populate, stride_bytes, false));
-    if (sink.is_open())
-        reserver->start((!streaming && text_size > (256u << 20)) ? (uint64_t)text_size / 4 : 0);
+    mapped.start_reserving(populate_threads, stride_bytes, (!streaming && text_size > (256u << 20)) ? (uint64_t)text_size / 4 : 0);
     {
         uint64_t early_min = 1ull << 30;
         if (const char* e = knob("TGSF_DOWN_EARLY_MIN")) early_min = strtoull(e, nullptr, 10);          // tests: small inputs too
         if (o.downsample && !streaming && in.mapped() && (uint64_t)text_size >= early_min) {
             uint64_t spec = (uint64_t)text_size / 4;
             if (o.genome_size > 0 && o.desired_depth > 0) spec = std::min<uint64_t>(spec, (2 * o.genome_size * (uint64_t)o.desired_depth) / (uint64_t)link.world + (uint64_t)text_size / 64);
-            open_dsink(4 * (uint64_t)text_size + (1ull << 30), spec);
+            open_down_mapped(4 * (uint64_t)text_size + (1ull << 30), spec);
         }
     }
     // Mappings of written batches (input text, output file).  One process (the default): the teardown is on the caller's
@@ -232,31 +225,13 @@ void Run::filter_pass()
     const bool sync_exit = !detached();                              // one process (the default): the teardown is on the clock
     release_input = sync_exit && !streaming && in.mapped() && !o.downsample;
     release_output = sync_exit || streaming;
-    const uint64_t release_piece = 16u << 20;
-    to_release.reset(new Channel<std::pair<const char*, uint64_t>>(1 << 16));
-    std::thread releaser([this, release_piece] {
-        CpuScope cpu(CPU_RELEASER);
-        for (;;) {
-            const std::pair<const char*, uint64_t> r = to_release->get();
-            if (!r.first) break;
-            for (uint64_t o2 = 0; o2 < r.second; o2 += release_piece) MappedSink::release(r.first + o2, std::min<uint64_t>(release_piece, r.second - o2));
-        }
-    });
+    mapped.start_filling(fill_threads, 16u << 20);
     std::thread writer([this] { writer_body(); });
     reader.join();
     for (std::thread& f : feeders) f.join();
     writer.join();
-    reserver->finish();
-    mapped_out = sink.is_open();
-    t_f0 = now_s();
-    pool->finish();
-    populate->finish();
-    to_release->put({nullptr, 0});
-    releaser.join();
-    t_busy = pool->busy_s();
-    t_fill_tail = now_s() - t_f0;
-    sink.close();
-    t_close = now_s() - t_f0 - t_fill_tail;
+    mapped_out = mapped.is_open();
+    mapped.finish();
     t_pipe = now_s() - t_p0;
 }
 

@@ -17,37 +17,42 @@ std::vector<uint64_t> pack_rows(const std::vector<uint64_t>& v, int32_t bc2, uin
     return out;
 }
 
-void add_rows(std::vector<uint64_t>& v, const std::vector<uint64_t>& ru, int32_t bc2, uint32_t nb2)
+// a whole tally vector added into another of the same layout: sums, the four "rows used" words are maxima; of the four
+// per-100-bp tables the rows that `part` uses (nothing was ever counted beyond them, and tgsf_counters_used leaves them unset)
+void add_tallies(std::vector<uint64_t>& v, const std::vector<uint64_t>& part, int32_t bc2, uint32_t nb2)
 {
-    const size_t head = tgsf_ctr_bin_table(0, bc2, nb2);
-    if (ru.size() < head) die("a rank of the job sent a tally vector of another layout");
     uint64_t rows[4];
-    for (int q = 0; q < 4; q++) rows[q] = std::max(v[TGSF_CTR_ROWS + q], ru[TGSF_CTR_ROWS + q]);
-    for (size_t i = 0; i < head; i++) v[i] += ru[i];
-    size_t from = head;
+    for (int q = 0; q < 4; q++) rows[q] = std::max(v[TGSF_CTR_ROWS + q], part[TGSF_CTR_ROWS + q]);
+    const size_t head = tgsf_ctr_bin_table(0, bc2, nb2);
+    for (size_t i = 0; i < head; i++) v[i] += part[i];
     for (int b = 0; b < 4; b++) {
-        const size_t at = tgsf_ctr_bin_table(b, bc2, nb2), n = (size_t)std::min<uint64_t>(ru[TGSF_CTR_ROWS + (b >> 1)], nb2) * 5;
-        if (from + n > ru.size()) die("a rank of the job sent a tally vector of another layout");
-        for (size_t i = 0; i < n; i++) v[at + i] += ru[from + i];
-        from += n;
+        const size_t at = tgsf_ctr_bin_table(b, bc2, nb2), n = (size_t)std::min<uint64_t>(part[TGSF_CTR_ROWS + (b >> 1)], nb2) * 5;
+        for (size_t i = 0; i < n; i++) v[at + i] += part[at + i];
     }
     for (int q = 0; q < 4; q++) v[TGSF_CTR_ROWS + q] = rows[q];
 }
 
-// this context's tallies added into v (sums; the four "rows used" words are maxima); of the bin tables only the rows in use travel
+void add_rows(std::vector<uint64_t>& v, const std::vector<uint64_t>& ru, int32_t bc2, uint32_t nb2)
+{
+    const size_t head = tgsf_ctr_bin_table(0, bc2, nb2);
+    if (ru.size() < head) die("a rank of the job sent a tally vector of another layout");
+    std::vector<uint64_t> whole(v.size(), 0);                          // pack_rows undone
+    std::copy(ru.begin(), ru.begin() + (long)head, whole.begin());
+    size_t from = head;
+    for (int b = 0; b < 4; b++) {
+        const size_t at = tgsf_ctr_bin_table(b, bc2, nb2), n = (size_t)std::min<uint64_t>(ru[TGSF_CTR_ROWS + (b >> 1)], nb2) * 5;
+        if (from + n > ru.size()) die("a rank of the job sent a tally vector of another layout");
+        std::copy(ru.begin() + (long)from, ru.begin() + (long)(from + n), whole.begin() + (long)at);
+        from += n;
+    }
+    add_tallies(v, whole, bc2, nb2);
+}
+
+// this context's tallies added into v; of the bin tables only the rows in use travel from the device
 static void add_context(const Api& L, tgsf_ctx* c, std::vector<uint64_t>& v, std::vector<uint64_t>& part, int32_t bc, uint32_t nbins)
 {
-    uint64_t used[2] = {0, 0};
-    if (L.counters_used(c, part.data(), part.size(), used) != TGSF_OK) die(L.last_error(c));
-    uint64_t rows[4];
-    for (int k = 0; k < 4; k++) rows[k] = std::max(v[TGSF_CTR_ROWS + k], part[TGSF_CTR_ROWS + k]);
-    const size_t head = tgsf_ctr_bin_table(0, bc, nbins);
-    for (size_t i = 0; i < head; i++) v[i] += part[i];
-    for (int b = 0; b < 4; b++) {
-        const size_t at = tgsf_ctr_bin_table(b, bc, nbins), n = (size_t)used[b >> 1] * 5;
-        for (size_t i = 0; i < n; i++) v[at + i] += part[at + i];
-    }
-    for (int k = 0; k < 4; k++) v[TGSF_CTR_ROWS + k] = rows[k];
+    if (L.counters_used(c, part.data(), part.size(), nullptr) != TGSF_OK) die(L.last_error(c));
+    add_tallies(v, part, bc, nbins);
 }
 
 // One process per GPU: the job's tallies = the sum over the ranks (src/TGSFilter.cpp:3208-3213 across GPUs).
@@ -294,14 +299,16 @@ void Run::timing_lines()
 {
     const Api& L = *api;
     if (timing) {
+        Pool& fills = mapped.pool();
+        const double t_busy = fills.busy_s();
         fprintf(stderr, "POOL: %zu jobs, busy %.3f, freeing job state %.3f, longest job %.3f, first job at %.3f, last job done at %.3f (pipeline start = 0, planner done at %.3f)\n",
-                pool->jobs_, t_busy, pool->destroy_, pool->longest_, pool->first_ - t_p0, pool->last_ - t_p0, t_f0 - t_p0);
+                fills.jobs_, t_busy, fills.destroy_, fills.longest_, fills.first_ - t_p0, fills.last_ - t_p0, mapped.t_planned - t_p0);
         fprintf(stderr, "TIMING: total %.3f s | index+prepass %.3f | waiting for the library %.3f (load %.3f + device %.3f, beside the pre-pass) | "
                         "pipeline %.3f (batching %.3f, tgsf_submit summed over %zu feeders %.3f, plan+write %.3f, planner waiting %.3f, "
                         "first batch filtered after %.3f, fill tail %.3f, closing the output %.3f; stages overlap) | stats+report %.3f | %s (fallocate %.3f, mapping the reserved pages %.3f, fill threads busy %.3f summed)\n",
                 now_s() - t_start, t_prepass, t_libwait, t_load, t_dev, t_pipe, t_parse, ctxs.size(), t_gpu, t_write, t_widle, t_first,
-                t_fill_tail, t_close, now_s() - t_p0 - t_pipe, mapped_out ? "output: fallocate + mapped fill" : "output: writev", sink.t_falloc, reserver->t_populate_wait, t_busy);
-        fprintf(stderr, "RESERVE: planner waited %.3f s for pages of the output file\n", t_drain);
+                mapped.t_fill_tail, mapped.t_close, now_s() - t_p0 - t_pipe, mapped_out ? "output: fallocate + mapped fill" : "output: writev", mapped.sink.t_falloc, mapped.t_populate_wait(), t_busy);
+        fprintf(stderr, "RESERVE: planner waited %.3f s for pages of the output file\n", mapped.t_claim_wait);
     }
     if (timing) {
         // kernel time of the run: the stage durations of every batch (HIP events inside the library), summed over the

@@ -131,19 +131,12 @@ void Run::open_output_early()
     // (a rank of a sharded job writes its own part: the parts, concatenated in rank order, are the single process's file)
     out_path = sharded && !o.out_file.empty() ? o.out_file + ".part" + std::to_string(link.rank) : o.out_file;
     {
-        const char* w = getenv("TGSF_WRITER");                         // "writev": always the single-stream writer
         uint64_t early_min = 256ull << 20;
         if (const char* e = knob("TGSF_EARLY_OPEN_MIN")) early_min = strtoull(e, nullptr, 10);           // tests: small inputs too
-        const bool may_map_early = !o.only_qc && !o.out_gz && !o.downsample && (o.filter || o.only_qc) && !o.out_file.empty() &&
-                                   !(w && !strcmp(w, "writev")) && !o.only_adapters && !streaming && in.mapped() &&
-                                   (uint64_t)text_size >= early_min;
-        if (may_map_early && sink.open(out_path, 4 * (uint64_t)text_size + (1ull << 30), true))
-            early = std::thread([this] {
-                CpuScope cpu(CPU_FALLOCATE);
-                const uint64_t limit = (uint64_t)text_size / 4;        // what a run keeps is not known yet; a surplus is cut off at the end
-                while (!early_stop.load() && sink.reserved() < limit)
-                    if (!sink.reserve_to(std::min<uint64_t>(limit, sink.reserved() + (256u << 20)), false)) break;   // (a nearly full file system: not this thread's call)
-            });
+        const bool may_map_early = plain_file_out() && !o.only_qc && !o.downsample && (o.filter || o.only_qc) &&
+                                   !o.only_adapters && !streaming && in.mapped() && (uint64_t)text_size >= early_min;
+        if (may_map_early && mapped.open(out_path, 4 * (uint64_t)text_size + (1ull << 30), true))
+            mapped.reserve_early((uint64_t)text_size / 4);             // what a run keeps is not known yet; a surplus is cut off at the end
     }
 }
 

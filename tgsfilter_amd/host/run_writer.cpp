@@ -1,32 +1,22 @@
 // run_writer.cpp -- the output side of the filter pass (run.h): the ordered planner and the fill jobs; the early sink of a
 // downsampling run.
+#include "record_out.h"
 #include "run.h"
 
 namespace host {
 
+bool Run::plain_file_out() const
+{
+    const char* w = getenv("TGSF_WRITER");                             // "writev": always the single-stream writer
+    return !o.out_gz && !o.out_file.empty() && !(w && !strcmp(w, "writev"));
+}
+
 // records [lo, hi) of the batch's layout copied into the mapped output file
 void Run::fill_job(const std::shared_ptr<Batch>& b, size_t lo, size_t hi)
 {
-    using Emit = Batch::Emit;
     Batch& bb = *b;
-    std::string nm;
-    for (size_t i = lo; i < hi; i++) {
-        const Emit& e = bb.em[i];
-        const Rec& rec = bb.recs[e.read];
-        const tgsf_fragment& fr = bb.frags[e.frag];
-        char* d = bb.dst + e.at;
-        *d++ = fastq_out ? '@' : '>';
-        if (e.pass_num < 2) { memcpy(d, rec.name, rec.name_len); d += rec.name_len; }
-        else { nm.clear(); append_name(nm, std::string_view(rec.name, rec.name_len), e.pass_num); memcpy(d, nm.data(), nm.size()); d += nm.size(); }
-        *d++ = '\n';
-        stream_copy(d, rec.seq + fr.start, (size_t)fr.len); d += fr.len;
-        if (fastq_out) {
-            memcpy(d, "\n+\n", 3); d += 3;
-            stream_copy(d, rec.qual + fr.start, (size_t)fr.len); d += fr.len;
-        }
-        *d++ = '\n';
-    }
-    stream_fence();
+    const auto at = [&](size_t i) { return i < bb.em.size() ? bb.em[i].at : bb.out_bytes; };
+    fill_records(bb.dst + at(lo), bb.dst + at(hi), lo, hi, fastq_out, [&](size_t i) -> const CleanRec& { return bb.em[i].rec; });
     if (--bb.left == 0) batch_done(b);
 }
 
@@ -37,7 +27,6 @@ void Run::writer_body()
 {
     using Emit = Batch::Emit;
     CpuScope cpu(CPU_PLANNER);
-    const std::string lead(1, fastq_out ? '@' : '>'), nl("\n"), sep("\n+\n");
     std::string name;
     std::map<uint64_t, std::shared_ptr<Batch>> held;               // batches that arrived ahead of their turn
     uint64_t want = 0, in_seen = 0;
@@ -56,7 +45,7 @@ void Run::writer_body()
         }
         want++;
         const double w0 = now_s();
-        const bool fill = sink.is_open();
+        const bool fill = mapped.is_open();
         uint64_t at = 0;
         for (size_t r = 0; r < b->recs.size(); r++) {
             int pass_num = 1;
@@ -66,55 +55,27 @@ void Run::writer_body()
             for (uint32_t f = rr.frag_begin; f < rr.frag_begin + rr.n_frags; f++) {
                 const tgsf_fragment& fr = b->frags[f];
                 if (!(fr.flags & TGSF_FF_PASS)) continue;
-                if (o.downsample) {                                // kept in memory instead of a tmp file (:3129-3137)
-                    clean_recs.push_back({rname, pass_num++, rec.seq + fr.start, rec.qual + fr.start, (uint32_t)fr.len});
-                    clean_bases += (uint64_t)fr.len;
-                    clean_lens.push_back(fr.len);
-                    continue;
-                }
+                const CleanRec c{rname, pass_num++, rec.seq + fr.start, rec.qual + fr.start, (uint32_t)fr.len};
                 clean_bases += (uint64_t)fr.len;
                 clean_lens.push_back(fr.len);
-                if (o.only_qc) { pass_num++; continue; }
-                if (fill) {
-                    b->em.push_back({(uint32_t)r, f, pass_num, at});
-                    size_t nlen = rname.size();
-                    if (pass_num >= 2) { int v = pass_num; nlen += 1; while (v) { nlen++; v /= 10; } }
-                    at += 1 + nlen + 1 + (uint64_t)fr.len + (fastq_out ? 3 + (uint64_t)fr.len : 0) + 1;
-                    pass_num++;
-                    continue;
-                }
-                out.text(lead);
-                if (pass_num < 2) out.piece(rname.data(), rname.size());
-                else { name.clear(); append_name(name, rname, pass_num); out.text(name); }
-                pass_num++;
-                out.text(nl);
-                out.piece(rec.seq + fr.start, (size_t)fr.len);
-                if (fastq_out) {
-                    out.text(sep);
-                    out.piece(rec.qual + fr.start, (size_t)fr.len);
-                }
-                out.text(nl);
-                out.end_record();
+                if (o.downsample) clean_recs.push_back(c);         // kept in memory instead of a tmp file (:3129-3137)
+                else if (o.only_qc) continue;
+                else if (fill) {
+                    b->em.push_back({c, at});
+                    at += record_bytes(c, fastq_out);
+                } else gather_record(out, c, fastq_out, name);
             }
         }
         in_seen += b->span;
         if (fill && at) {
-            if (sink.planned() + at > sink.capacity()) die("output more than four times the size of the input: larger than the space mapped for it (TGSF_WRITER=writev writes such a file)");
-            {
-                // How far the file will go: what is left of the input times the share of it that was written so far
-                // (plus a little).  (A streamed input's text size is estimated from the share of the file decoded so far.)
-                const double share = in_seen ? (double)(sink.planned() + at) / (double)in_seen : 1.0;
-                const double sh = stream_share.load();
-                const uint64_t in_total = !streaming ? (uint64_t)text_size
-                                        : (uint64_t)((double)stream_text.load() / (sh > 1e-6 ? sh : 1e-6));
-                uint64_t goal = sink.planned() + at + (uint64_t)(share * 1.02 * (double)(in_total - std::min<uint64_t>(in_seen, in_total)));
-                goal = std::min<uint64_t>(std::max<uint64_t>(goal, sink.planned() + at), sink.capacity());
-                reserver->want(goal, sink.planned() + at);
-                const double d0 = now_s();
-                reserver->wait_ready(sink.planned() + at);            // instantiated AND mapped: the fill jobs take no fault
-                t_drain += now_s() - d0;
-            }
-            b->dst = sink.place(at);
+            // How far the file will go: what is left of the input times the share of it that was written so far
+            // (plus a little).  (A streamed input's text size is estimated from the share of the file decoded so far.)
+            const uint64_t end = mapped.sink.planned() + at;
+            const double share = in_seen ? (double)end / (double)in_seen : 1.0;
+            const double sh = stream_share.load();
+            const uint64_t in_total = !streaming ? (uint64_t)text_size
+                                    : (uint64_t)((double)stream_text.load() / (sh > 1e-6 ? sh : 1e-6));
+            b->dst = mapped.claim(at, end + (uint64_t)(share * 1.02 * (double)(in_total - std::min<uint64_t>(in_seen, in_total))));
             b->out_bytes = at;
             const size_t n = b->em.size();
             const int parts = (int)std::min<size_t>((size_t)fill_threads, std::max<size_t>(1, at / fill_min));
@@ -127,7 +88,7 @@ void Run::writer_body()
                     hi = (size_t)(std::lower_bound(b->em.begin() + (long)lo, b->em.end(), target,
                                                    [](const Emit& e, uint64_t tgt) { return e.at < tgt; }) - b->em.begin());
                 }
-                pool->add([this, b, lo, hi] { fill_job(b, lo, hi); });
+                mapped.fill([this, b, lo, hi] { fill_job(b, lo, hi); });
                 lo = hi;
             }
         }
@@ -142,16 +103,10 @@ void Run::writer_body()
 // :2297-2344) -- but the file can be instantiated meanwhile: while the filter pass is busy with the link to the device,
 // pages for what the selection may keep are reserved and mapped (a quarter of the input at most, and no more than twice
 // the bases asked for with -g/-d; a surplus is cut off at the end).  Large plain outputs only.
-bool Run::open_dsink(uint64_t capacity, uint64_t speculative)
+bool Run::open_down_mapped(uint64_t capacity, uint64_t speculative)
 {
-    const char* w = getenv("TGSF_WRITER");
-    if (o.out_gz || o.out_file.empty() || (w && !strcmp(w, "writev"))) return false;
-    std::unique_ptr<MappedSink> d(new MappedSink);
-    if (!d->open(out_path, capacity)) return false;
-    dsink = std::move(d);
-    dpop.reset(new Pool(populate_threads, CPU_POPULATE));
-    dres.reset(new Reserver(*dsink, *dpop, stride_bytes, false));
-    dres->start(speculative);
+    if (!plain_file_out() || !down_mapped.open(out_path, capacity)) return false;
+    down_mapped.start_reserving(populate_threads, stride_bytes, speculative);
     return true;
 }
 
