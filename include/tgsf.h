@@ -112,6 +112,8 @@ typedef struct tgsf_params {
  * stands for its value - 256.  A read whose mean of those values falls outside
  * [0, 256) fails the batch with TGSF_E_DATA: the reference indexes
  * rawDiffQualReadsBases[int(mean)] out of bounds there (:1943).
+ * The offsets themselves are the caller's duty: the library does not check
+ * that a read lies inside n_bytes, nor that reads do not overlap or run backwards.
  */
 typedef struct tgsf_batch_in {
     const uint8_t*  seq;
@@ -251,6 +253,12 @@ void tgsf_destroy(tgsf_ctx* ctx);
  * batch: out->n_frags is set, the fragment records are copied, asynchronous errors are reported.  One
  * batch may be pending per context; several contexts overlap each other's copies and kernels (copies are
  * only asynchronous from pinned host memory).  tgsf_submit = tgsf_submit_async + tgsf_wait.
+ *
+ * A call refused before anything was enqueued -- TGSF_E_INVALID or TGSF_E_CAPACITY returned by
+ * tgsf_submit_async or tgsf_submit_device itself: a null pointer, an empty batch, more reads or bytes than the
+ * context was sized for, qual_offsets without lengths, misaligned device pointers, a batch already pending (which
+ * then completes as if alone) -- writes nothing and leaves the context and its tallies exactly as they were.
+ * What a batch refused LATER, by tgsf_wait (tgsf_submit includes it), leaves behind: see tgsf_wait.
  */
 int tgsf_submit(tgsf_ctx* ctx, const tgsf_batch_in* in, tgsf_batch_out* out);
 int tgsf_submit_async(tgsf_ctx* ctx, const tgsf_batch_in* in, tgsf_batch_out* out);
@@ -277,13 +285,30 @@ int tgsf_submit_device(tgsf_ctx* ctx, const tgsf_batch_in* in, tgsf_batch_out* o
                        uint32_t* d_n_frags, void* hip_stream);
 
 /* Block until everything submitted on this context has finished; run again the batches whose candidate pool
- * overflowed (see tgsf_submit_device); complete a pending tgsf_submit_async batch; report async errors. */
+ * overflowed (see tgsf_submit_device); complete a pending tgsf_submit_async batch; report async errors.
+ *
+ * After a refusal by tgsf_wait nothing is pending any more, the context stays usable, and the records and
+ * fragments of the batches submitted afterwards do not depend on the refused one.  The refused batch's own
+ * records and fragments are unspecified (but see TGSF_E_CAPACITY).  Its share of the tallies, by the reason:
+ *   TGSF_E_DATA, "length 0 or above max_read_len" (one read or several): the reads of such a length are left
+ *     out; the batch's other reads HAVE been tallied, exactly as a batch of them alone would have been.
+ *   TGSF_E_DATA, "mean quality outside [0,256)": the batch has added an unspecified part of itself.
+ *   TGSF_E_CAPACITY from frag_capacity alone (a host batch: "produced N fragments, caller provided room for
+ *     M", with out->n_frags = N and out->reads complete, no fragment copied; a tgsf_submit_device batch:
+ *     "fragment capacity exceeded (N)"): the batch HAS been tallied in full.  Submitting it again with more
+ *     room counts it twice: call tgsf_reset_counters first, or take its tallies as they are.
+ *   TGSF_E_INVALID from the tgsf_submit_device call that found TGSF_MAX_ENQUEUED batches enqueued, one of which
+ *     has to be run again: that call's batch was not enqueued; the enqueued ones are forgotten, their results
+ *     and their share of the tallies unspecified.
+ * In every case tgsf_reset_counters makes the context as new: the tallies of the batches submitted after it
+ * are exactly theirs. */
 int tgsf_wait(tgsf_ctx* ctx);
 
 /* Number of uint64 words tgsf_counters() writes, and the table geometry. */
 int tgsf_counters_len(tgsf_ctx* ctx, uint64_t* n_words, int32_t* bc_len, uint32_t* n_bins);
-/* Copy the tallies to host memory (synchronises the context). Replaces the
- * per-thread merge of src/TGSFilter.cpp:3208-3213 / :2673-2725 / :2586-2597. */
+/* Copy the tallies to host memory (synchronises the context: as tgsf_wait, with its refusals). Replaces the
+ * per-thread merge of src/TGSFilter.cpp:3208-3213 / :2673-2725 / :2586-2597.  n_words below
+ * tgsf_counters_len's is TGSF_E_CAPACITY and dst is not written. */
 int tgsf_counters(tgsf_ctx* ctx, uint64_t* dst, uint64_t n_words);
 /* Same, but of the four bin tables ([n_bins][5] each, n_bins sized by max_read_len at tgsf_create -- possibly far
  * more rows than any read of the run needed) only the rows in use are copied: rows[0] rows of the two raw tables,

@@ -20,15 +20,16 @@ def sized(p: abi.Params, reads, extra=1):
     return p
 
 
-def compare_batch(ctx: capi.Context, p: abi.Params, reads, *, align=16, explicit_lengths=True):
-    """Run one batch through the backend and the oracle; everything must be identical."""
+def compare_batch(ctx: capi.Context, p: abi.Params, reads, *, align=16, explicit_lengths=True, base=None):
+    """Run one batch through the backend and the oracle; everything must be identical.  base: the tallies the context
+    held before the batch (None: none) -- the oracle adds the batch to a copy of them."""
     seq, qual, offsets, lengths = synth.pack(reads, align=align)
     if explicit_lengths:
         got_r, got_f = ctx.submit(seq, qual, offsets[:-1].copy() if align > 1 else offsets, lengths)
     else:
         got_r, got_f = ctx.submit(seq, qual, offsets, None)
     ctr = ctx.counters()
-    exp_ctr = np.zeros(ctx.ctr_words, dtype=np.uint64)
+    exp_ctr = np.zeros(ctx.ctr_words, dtype=np.uint64) if base is None else base.copy()
     exp_r, exp_f, exp_ctr = orc.filter_batch(p, seq, qual, offsets, lengths if explicit_lengths else None,
                                              n_bins=ctx.n_bins, ctr=exp_ctr)
     for name in ("sum_q", "flags", "n_frags", "frag_begin", "trimmed"):
@@ -190,20 +191,22 @@ def fastq_text_layout(reads):
     return text, np.array(off, np.uint64), np.array(qoff, np.uint64), np.array(ln, np.uint32)
 
 
-def compare_batch_in_place(ctx: capi.Context, p: abi.Params, reads):
+def compare_batch_in_place(ctx: capi.Context, p: abi.Params, reads, base=None):
     """seq == qual == the FASTQ text itself, two offset arrays: must equal the oracle on the same layout
-    (and therefore the packed layout, which the oracle is indifferent to)."""
+    (and therefore the packed layout, which the oracle is indifferent to).  base: as in compare_batch."""
     text, off, qoff, ln = fastq_text_layout(reads)
     got_r, got_f = ctx.submit(text, text, off, ln, qual_offsets=qoff)
     ctr = ctx.counters()
-    exp_r, exp_f, exp_ctr = orc.filter_batch(p, text, text, off, ln, n_bins=ctx.n_bins, qual_offsets=qoff)
+    exp_r, exp_f, exp_ctr = orc.filter_batch(p, text, text, off, ln, n_bins=ctx.n_bins, qual_offsets=qoff,
+                                             ctr=None if base is None else base.copy())
     assert np.array_equal(got_r, exp_r)
     assert np.array_equal(got_f, exp_f)
     bad = np.nonzero(ctr != exp_ctr)[0]
     assert bad.size == 0, f"tally words differ at {bad[:12]}: got {ctr[bad[:12]]} exp {exp_ctr[bad[:12]]}"
     seq, qual, offsets, lengths = synth.pack(reads)
-    pk_r, pk_f, pk_ctr = orc.filter_batch(p, seq, qual, offsets, lengths, n_bins=ctx.n_bins)
+    pk_r, pk_f, pk_ctr = orc.filter_batch(p, seq, qual, offsets, lengths, n_bins=ctx.n_bins, ctr=None if base is None else base.copy())
     assert np.array_equal(pk_ctr, exp_ctr) and np.array_equal(pk_f, exp_f)
+    return got_r, got_f, ctr
 
 
 def repeat_reads(seed=51, n=60):

@@ -70,6 +70,87 @@ def test_parameter_validation(lib):
     assert ei.value.code == abi.E_UNSUPPORTED
 
 
+def _create_params(**kw):
+    """Parameters tgsf_create accepts (two adapters, the repeat gate on), with fields overwritten AFTER make_params' own clamps."""
+    p = abi.make_params("ont", adapters=[synth.ONT_RAPID, synth.ONT_RAPID_RC], min_repeat=5, kmer=11,
+                        max_batch_bases=1000, max_batch_reads=4, max_read_len=500)
+    for k, v in kw.items():
+        if k == "adapter0":                     # (pointer, length) of the first adapter
+            p.adapters[0], p.adapter_len[0] = v
+        else:
+            setattr(p, k, v)
+    return p
+
+
+_NAN = float("nan")
+# one row per check of tgsf_create, in its order: (fields, the status include/tgsf.h names for that class, the field's name in
+# tgsf_params as the message holds it -- the offending field's and no other's: see test_create_refuses)
+CREATE_REFUSALS = [
+    (dict(struct_size=C.sizeof(abi.Params) - 8), abi.E_INVALID, "struct_size"),
+    (dict(struct_size=0), abi.E_INVALID, "struct_size"),
+    (dict(n_adapters=-1), abi.E_INVALID, "n_adapters"),
+    (dict(n_adapters=33), abi.E_INVALID, "n_adapters"),
+    (dict(kmer=0), abi.E_UNSUPPORTED, "kmer (-k) 0"),
+    (dict(kmer=33), abi.E_UNSUPPORTED, "kmer (-k) 33"),
+    (dict(qtype=32), abi.E_INVALID, "qtype"),
+    (dict(bc_len=-1), abi.E_INVALID, "bc_len"),
+    (dict(bc_len=(1 << 20) + 1), abi.E_INVALID, "bc_len"),
+    (dict(end_sim=0.0), abi.E_INVALID, "end_sim"),
+    (dict(end_sim=_NAN), abi.E_INVALID, "end_sim"),
+    (dict(mid_sim=0.0), abi.E_INVALID, "mid_sim"),
+    (dict(mid_sim=_NAN), abi.E_INVALID, "mid_sim"),
+    (dict(end_len=-1), abi.E_INVALID, "end_len"),
+    (dict(extra_len=-1), abi.E_INVALID, "extra_len"),
+    (dict(end_match_len=0), abi.E_INVALID, "end_match_len"),
+    (dict(mid_match_len=0), abi.E_INVALID, "mid_match_len"),
+    (dict(adapter0=(synth.ONT_RAPID, 0)), abi.E_UNSUPPORTED, "adapter 0"),
+    (dict(adapter0=(None, 50)), abi.E_UNSUPPORTED, "adapter 0"),
+    (dict(max_batch_bases=0), abi.E_INVALID, "max_batch_bases"),
+    (dict(max_batch_reads=0), abi.E_INVALID, "max_batch_reads"),
+    (dict(max_read_len=0), abi.E_INVALID, "max_read_len"),
+    (dict(max_read_len=(1 << 28) + 1), abi.E_INVALID, "max_read_len"),
+]
+# the accepting neighbours that are cheap (small contexts; no context with max_read_len near 2^28 is created)
+CREATE_ACCEPTED = [dict(kmer=1), dict(kmer=32), dict(kmer=0, min_repeat=0), dict(kmer=33, min_repeat=0), dict(qtype=33), dict(qtype=64),
+                   dict(bc_len=0), dict(end_len=0, extra_len=0), dict(end_match_len=1, mid_match_len=1)]
+
+
+@pytest.mark.parametrize("fields,code,names", CREATE_REFUSALS, ids=lambda v: "-".join("%s=%s" % kv for kv in v.items()) if isinstance(v, dict) else None)
+def test_create_refuses(lib, fields, code, names):
+    """Every check of tgsf_create in front of the device: the status of its class, no context, and a message from
+    tgsf_last_error(NULL) that names the field."""
+    p = _create_params(**fields)
+    h = C.c_void_p(0xDEAD)
+    rc = lib.tgsf_create(C.byref(p), 0, C.byref(h))
+    msg = lib.tgsf_last_error(None).decode()
+    assert rc == code, (rc, msg)
+    assert h.value is None                         # *out_ctx is NULL after a refusal
+    assert names in msg, msg
+    # ... and no other field of tgsf_params: the message tells WHICH of two similarities, lengths or sizing hints it was
+    others = [f for f, _ in abi.Params._fields_ if re.search(r"\b%s\b" % f, msg) and not re.search(r"\b%s\b" % f, names)]
+    assert not others, (others, msg)
+
+
+def test_create_refuses_null_arguments(lib):
+    h = C.c_void_p()
+    assert lib.tgsf_create(None, 0, C.byref(h)) == abi.E_INVALID and "null argument" in lib.tgsf_last_error(None).decode()
+    assert lib.tgsf_create(C.byref(_create_params()), 0, None) == abi.E_INVALID and "null argument" in lib.tgsf_last_error(None).decode()
+
+
+@pytest.mark.parametrize("fields", CREATE_ACCEPTED, ids=lambda v: "-".join("%s=%s" % kv for kv in v.items()))
+def test_create_accepts_the_neighbours(lib, fields):
+    """... and the values next to the refused ones pass every check: on a box without a device that shows as
+    TGSF_E_NO_DEVICE (the device is looked for after the checks), with one as a context."""
+    p = _create_params(**fields)
+    h = C.c_void_p()
+    rc = lib.tgsf_create(C.byref(p), 0, C.byref(h))
+    assert rc in (abi.OK, abi.E_NO_DEVICE), (rc, lib.tgsf_last_error(None).decode())
+    if rc == abi.OK:
+        lib.tgsf_destroy(h)
+    else:
+        assert "no CPU fallback" in lib.tgsf_last_error(None).decode()
+
+
 def test_rccl_library_exports():
     """libtgsf_rccl.so (include/tgsf_rccl.h, the optional tally all-reduce) loads and exports what its header declares."""
     hdr = open(os.path.join(ROOT, "include", "tgsf_rccl.h")).read()

@@ -169,12 +169,14 @@ class Context:
         self._chk(self.lib.tgsf_counters(self.h, out.ctypes.data, self.ctr_words))
         return out
 
-    def counters_used(self):
-        """Like counters(), but only the rows in use of the bin tables travel (tgsf_counters_used)."""
-        out = np.zeros(self.ctr_words, dtype=np.uint64)
+    def counters_used(self, out=None, with_rows=True):
+        """Like counters(), but only the rows in use of the bin tables travel (tgsf_counters_used).  `out`: the caller's
+        own buffer (words beyond the rows in use are left as they were); with_rows=False passes rows == NULL."""
+        if out is None:
+            out = np.zeros(self.ctr_words, dtype=np.uint64)
         rows = (C.c_uint64 * 2)()
-        self._chk(self.lib.tgsf_counters_used(self.h, out.ctypes.data, self.ctr_words, rows))
-        return out, (rows[0], rows[1])
+        self._chk(self.lib.tgsf_counters_used(self.h, out.ctypes.data, out.size, rows if with_rows else None))
+        return out, ((rows[0], rows[1]) if with_rows else None)
 
     def merge_from(self, other: "Context"):
         """Add the tallies of another context of this device to this one's, in HBM (tgsf_counters_merge)."""

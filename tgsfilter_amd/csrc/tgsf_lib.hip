@@ -382,21 +382,24 @@ extern "C" int tgsf_create(const tgsf_params* p, int device, tgsf_ctx** out)
     if (p->n_adapters < 0 || p->n_adapters > TGSF_MAX_ADAPTERS)
         return fail(nullptr, TGSF_E_INVALID, "n_adapters %d outside [0,%d]", p->n_adapters, TGSF_MAX_ADAPTERS);
     if (p->min_repeat > 0 && (p->kmer < 1 || p->kmer > 32))
-        return fail(nullptr, TGSF_E_UNSUPPORTED, "-k %d: the repeat gate supports k-mer sizes 1..32 (the reference's k-mers are 64 bits)", p->kmer);
+        return fail(nullptr, TGSF_E_UNSUPPORTED, "kmer (-k) %d: the repeat gate supports k-mer sizes 1..32 (the reference's k-mers are 64 bits)", p->kmer);
     if (p->qtype != 33 && p->qtype != 64) return fail(nullptr, TGSF_E_INVALID, "qtype must be 33 or 64");
     if (p->bc_len < 0 || p->bc_len > kMaxBcLenTotal) return fail(nullptr, TGSF_E_INVALID, "bc_len (-e) outside [0,%d]", kMaxBcLenTotal);
     if (p->filter && p->n_adapters > 0) {
-        if (!(p->end_sim > 0.f) || !(p->mid_sim > 0.f)) return fail(nullptr, TGSF_E_INVALID, "similarities must be > 0");
-        if (p->end_len < 0 || p->extra_len < 0) return fail(nullptr, TGSF_E_INVALID, "end_len / extra_len must be >= 0");
-        if (p->end_match_len < 1 || p->mid_match_len < 1)
-            return fail(nullptr, TGSF_E_INVALID, "match lengths must be >= 1");
+        if (!(p->end_sim > 0.f)) return fail(nullptr, TGSF_E_INVALID, "end_sim must be > 0");
+        if (!(p->mid_sim > 0.f)) return fail(nullptr, TGSF_E_INVALID, "mid_sim must be > 0");
+        if (p->end_len < 0) return fail(nullptr, TGSF_E_INVALID, "end_len must be >= 0");
+        if (p->extra_len < 0) return fail(nullptr, TGSF_E_INVALID, "extra_len must be >= 0");
+        if (p->end_match_len < 1) return fail(nullptr, TGSF_E_INVALID, "end_match_len must be >= 1");
+        if (p->mid_match_len < 1) return fail(nullptr, TGSF_E_INVALID, "mid_match_len must be >= 1");
     }
     for (int a = 0; a < p->n_adapters; a++) {
         if (!p->adapters[a] || p->adapter_len[a] < 1 || p->adapter_len[a] > TGSF_MAX_ADAPTER_LEN)
             return fail(nullptr, TGSF_E_UNSUPPORTED, "adapter %d: length %d outside [1,%d]", a, p->adapter_len[a], TGSF_MAX_ADAPTER_LEN);
     }
-    if (!p->max_batch_bases || !p->max_batch_reads || !p->max_read_len)
-        return fail(nullptr, TGSF_E_INVALID, "max_batch_bases / max_batch_reads / max_read_len must be set");
+    if (!p->max_batch_bases) return fail(nullptr, TGSF_E_INVALID, "max_batch_bases must be set");
+    if (!p->max_batch_reads) return fail(nullptr, TGSF_E_INVALID, "max_batch_reads must be set");
+    if (!p->max_read_len) return fail(nullptr, TGSF_E_INVALID, "max_read_len must be set");
     if (p->max_read_len > (1u << 28)) return fail(nullptr, TGSF_E_INVALID, "max_read_len above 2^28");
 
     tgsf_ctx* c = new tgsf_ctx();
