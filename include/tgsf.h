@@ -122,7 +122,9 @@ typedef struct tgsf_batch_in {
     const uint32_t* lengths;   /* optional, n_reads entries                           */
     uint32_t        n_reads;
     uint32_t        reserved;
-    uint64_t        n_bytes;   /* bytes spanned by seq / qual (>= last offset+len)    */
+    uint64_t        n_bytes;   /* bytes spanned by seq / qual (>= last offset+len); a host batch may pass 0: the
+                                * span is then taken from the offsets.  At most max_batch_bases + 16 * max_batch_reads
+                                * (room for reads padded to 16 bytes): more is TGSF_E_CAPACITY.                      */
     /* Optional: qualities of read i start at qual[qual_offsets[i]] instead of qual[offsets[i]]
      * (n_reads entries; requires `lengths`).  With seq == qual this lets both streams be read IN
      * PLACE from one buffer holding the raw FASTQ text: the caller only indexes the records. */
@@ -278,6 +280,11 @@ int tgsf_submit_async(tgsf_ctx* ctx, const tgsf_batch_in* in, tgsf_batch_out* ou
  * a location, include/edlib.cpp:660-672) is left alone by its first run and run again, from its inputs, inside
  * tgsf_wait.  A caller that only synchronises its stream and finds TGSF_NFRAGS_NOT_FINAL in *d_n_frags is looking at
  * such a batch: its records are not written yet.
+ *
+ * in->n_bytes is REQUIRED here: the offsets are in device memory, so the host cannot derive the span from them, and the
+ * span sizes launches and bounds every per-chunk buffer of the context.  n_bytes == 0 is TGSF_E_INVALID; n_bytes above
+ * max_batch_bases + 16 * max_batch_reads is TGSF_E_CAPACITY ("batch spans N bytes, context was sized for M bases"), as
+ * from tgsf_submit_async -- both before anything is enqueued.
  */
 #define TGSF_MAX_ENQUEUED 64
 #define TGSF_NFRAGS_NOT_FINAL 0xFFFFFFFFu

@@ -136,8 +136,9 @@ int tgsf_text_fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf
  * tgsf_submit_device(ctx) runs with seq = qual = the device text and the device index, tgsf_wait(ctx), and the
  * per-read records, the fragments (batch_out->n_frags is set) and the index come down.  batch_out->reads needs room
  * for max_records entries or for the records the text holds.  ctx must live on the same device; create it with
- * no_qual for FASTA.  What libtgsf refuses -- more records than its max_batch_reads (TGSF_E_CAPACITY), a read above
- * its max_read_len (TGSF_E_DATA), too few fragment slots (TGSF_E_CAPACITY) -- is handed through with its code and
+ * no_qual for FASTA.  What libtgsf refuses -- more records than its max_batch_reads (TGSF_E_CAPACITY), a text larger
+ * than the context's max_batch_bases + 16 * max_batch_reads (TGSF_E_CAPACITY: the text's n_bytes is the batch's span, the
+ * filter has not run), a read above its max_read_len (TGSF_E_DATA), too few fragment slots (TGSF_E_CAPACITY) -- is handed through with its code and
  * tgsf_last_error(ctx)'s text; the object stays usable.  n_records == 0 is no error: nothing runs, n_frags = 0.
  * Only the regular prefix is filtered: look at out_summary->stop and ->consumed.
  */

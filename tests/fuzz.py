@@ -6,7 +6,7 @@ import os
 
 import numpy as np
 
-from tests import parity
+from tests import parity, sizing
 from tgsfilter_amd import abi, capi, synth
 
 LIB_ADAPTERS = [synth.ONT_RAPID, synth.ONT_RAPID_RC, synth.PACBIO_BLUNT, synth.PACBIO_BLUNT_RC,
@@ -77,6 +77,10 @@ def random_case(seed: int, n_reads: int):
         if r2.random() < 0.5:                                             # (the by-product beside the repeat gate: round 6)
             kw.pop("min_repeat", None); kw.pop("kmer", None)
         kw["_force_by_product"] = bool(r2.random() < 0.7)
+    if os.environ.get("TGSF_FUZZ_SIZING") == "1":
+        # (the context sized as the product sizes it, tests/sizing.py, instead of cut to fit the batch -- again a stream of its own)
+        r3 = np.random.default_rng(seed ^ 0x0512E5ED)
+        kw["_sizing"] = str(r3.choice(["exact", "indexed", "streamed", str(r3.choice(list(sizing.SEAMS)))]))
     return kind, reads, kw
 
 
@@ -84,10 +88,11 @@ def run_case(lib_path, seed: int, n_reads: int):
     kind, reads, kw = random_case(seed, n_reads)
     pool_cap = kw.pop("_pool_cap", 0)
     force_bp = kw.pop("_force_by_product", False)
+    hints = kw.pop("_sizing", "exact")
     outer_ct = os.environ.get("TGSF_CLEAN_TABLES")
     if force_bp:
         os.environ["TGSF_CLEAN_TABLES"] = "byproduct"
-    p = parity.sized(abi.make_params(kind, **kw), reads)
+    p = sizing.size(abi.make_params(kind, **kw), reads, hints)
     outer = os.environ.get("TGSF_POOL_CAP")                 # (a campaign may set one for every case: keep it)
     if pool_cap:
         os.environ["TGSF_POOL_CAP"] = str(pool_cap)
@@ -107,6 +112,6 @@ def run_case(lib_path, seed: int, n_reads: int):
         parity.compare_batch(ctx, p, reads, align=int(np.random.default_rng(seed).choice([1, 16])),
                              explicit_lengths=True)
     except AssertionError as e:
-        raise AssertionError("fuzz seed %d (%s, %s): %s" % (seed, kind, {k: v for k, v in kw.items() if k != "adapters"}, e))
+        raise AssertionError("fuzz seed %d (%s, %s, sized %s): %s" % (seed, kind, {k: v for k, v in kw.items() if k != "adapters"}, hints, e))
     finally:
         ctx.close()

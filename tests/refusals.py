@@ -121,7 +121,7 @@ def records_equal(got_r, got_f, exp_r, exp_f, what=""):
 # 1. refusals decided on the host: nothing is enqueued, the tallies do not move, the context goes on
 # ---------------------------------------------------------------------------------------------------------------------
 def host_refusals(lib_path):
-    """check_batch, the output, span and pending-batch checks of tgsf_submit_async, the pointer checks of
+    """check_batch, the output, span and pending-batch checks of tgsf_submit_async, the span and pointer checks of
     tgsf_submit_device, the buffer checks of tgsf_counters / tgsf_counters_used, tgsf_counters_merge and
     tgsf_align_windows, on a context that
     already holds tallies: each refusal has the code include/tgsf.h names and a message that says what was wrong, leaves
@@ -166,9 +166,9 @@ def host_refusals(lib_path):
             ("n_reads 0", bi(n_reads=0), bo(), I, ["empty batch"]),
             ("n_reads cap + 1", bi(n_reads=cap_reads + 1), bo(), CAP, ["%u reads" % (cap_reads + 1), "sized for %u" % cap_reads]),
             ("qual_offsets without lengths", bi(lengths=None, offsets=off.ctypes.data, qual_offsets=off_n.ctypes.data), bo(), I, ["qual_offsets", "lengths"]),
+            ("span above the capacity", bi(n_bytes=cap_bases + 16 * cap_reads + 1), bo(), CAP, ["spans %u bytes" % (cap_bases + 16 * cap_reads + 1), "sized for %u bases" % cap_bases]),
         ]
         host_only = [
-            ("span above the capacity", bi(n_bytes=cap_bases + 16 * cap_reads + 1), bo(), CAP, ["spans %u bytes" % (cap_bases + 16 * cap_reads + 1)]),
             ("span from offsets and lengths", bi(n_bytes=0, offsets=far.ctypes.data), bo(), CAP, ["spans"]),
             ("span from the last offset", bi(n_bytes=0, offsets=far1.ctypes.data, lengths=None), bo(), CAP, ["spans"]),
             ("out->reads NULL", bi(), bo(reads=None), I, ["null output"]),
@@ -192,9 +192,13 @@ def host_refusals(lib_path):
         d_i, d_o = db.structs()
         for what, i_, o_, code, words in batch_cases:
             j = abi.BatchIn(d_i.seq if i_.seq else None, d_i.qual if i_.qual else None, d_i.offsets if i_.offsets else None,
-                            d_i.lengths if i_.lengths else None, i_.n_reads, 0, d_i.n_bytes, d_i.offsets if i_.qual_offsets else None)
+                            d_i.lengths if i_.lengths else None, i_.n_reads, 0, i_.n_bytes, d_i.offsets if i_.qual_offsets else None)
             refused(ctx, L.tgsf_submit_device(ctx.h, C.byref(j), C.byref(d_o), db.o_n[0], None), code, *words)
             unchanged("device: " + what)
+        # a device batch states its span: the offsets are on the device, the host cannot derive it from them
+        j = abi.BatchIn(d_i.seq, d_i.qual, d_i.offsets, d_i.lengths, d_i.n_reads, 0, 0, None)
+        refused(ctx, L.tgsf_submit_device(ctx.h, C.byref(j), C.byref(d_o), db.o_n[0], None), I, "n_bytes is 0")
+        unchanged("device: n_bytes 0")
         refused(ctx, L.tgsf_submit_device(ctx.h, C.byref(d_i), None, db.o_n[0], None), I, "null output")
         refused(ctx, L.tgsf_submit_device(ctx.h, C.byref(d_i), C.byref(abi.BatchOut(None, d_o.frags, d_o.frag_capacity, 0)), db.o_n[0], None), I, "null output")
         for seq_at, qual_at in ((1, 0), (8, 0), (0, 4), (0, 15)):
@@ -278,6 +282,52 @@ def host_refusals(lib_path):
         for o in others:
             o.close()
         ctx.close()
+
+
+def text_over_capacity(lib_path, text_lib_path):
+    """tgsf_text_submit hands its text's size to tgsf_submit_device as the batch's span: an object that holds more text
+    than the context takes (max_batch_bases + 16 * max_batch_reads) gets TGSF_E_CAPACITY through the text object, nothing
+    of the batch is enqueued or tallied, and the object and the context both go on -- the context with a text that fits,
+    the object with a context that takes the large one."""
+    from tests import textparity
+    from tgsfilter_amd import text as tgtext
+    reads = synth.make_reads(23, 40, "ont", mean_len=1500, max_len=5000, zoo=True, pmid=0.1)
+    small = reads[:8]
+    padded, off, qoff, ln = parity.fastq_text_layout(reads)
+    text = padded[:-64].tobytes()
+    s_padded, s_off, s_qoff, s_ln = parity.fastq_text_layout(small)
+    s_text = s_padded[:-64].tobytes()
+    p = abi.make_params("ont", adapters=ADS, min_q=7.0, min_len=100, head_trim=HEAD, tail_trim=TAIL)
+    p.max_batch_reads, p.max_read_len = len(reads), max(len(r[1]) for r in reads)
+    p.max_batch_bases = len(text) - 16 * len(reads) - 1               # one byte short of the whole text
+    assert p.max_batch_bases + 16 * p.max_batch_reads >= len(s_text)
+    big = abi.make_params("ont", adapters=ADS, min_q=7.0, min_len=100, head_trim=HEAD, tail_trim=TAIL)
+    big.max_batch_reads, big.max_read_len, big.max_batch_bases = p.max_batch_reads, p.max_read_len, len(text)
+    ctx = capi.Context(p, 0, lib_path)
+    ctx_big = capi.Context(big, 0, lib_path)
+    tx = tgtext.TextIndexer(0, len(text), len(reads), text_lib_path)
+    try:
+        idx, s, r, f = tx.submit(ctx, s_text)
+        exp_r, exp_f, before = orc.filter_batch(p, s_padded, s_padded, s_off, s_ln, n_bins=ctx.n_bins, qual_offsets=s_qoff)
+        records_equal(r, f, exp_r, exp_f, "a text that fits")
+        assert_tallies(ctx, before, "a text that fits")
+        raises(lambda: tx.submit(ctx, text), abi.E_CAPACITY, "spans %u bytes" % len(text), "sized for %u bases" % p.max_batch_bases)
+        refused(ctx, ctx.lib.tgsf_wait(ctx.h), abi.OK)                 # nothing was enqueued
+        assert_tallies(ctx, before, "after the refused text")
+        idx, s, r, f = tx.submit(ctx, s_text)                          # the same object, the same context
+        exp_r, exp_f, now = orc.filter_batch(p, s_padded, s_padded, s_off, s_ln, n_bins=ctx.n_bins, qual_offsets=s_qoff, ctr=before.copy())
+        assert s["n_records"] == len(small) and s["stop"] == tgtext.END
+        records_equal(r, f, exp_r, exp_f, "the context after the refusal")
+        assert_tallies(ctx, now, "the context after the refusal")
+        idx, s, r, f = tx.submit(ctx_big, text)                        # the object still holds and indexes the large text
+        exp_r, exp_f, exp = orc.filter_batch(big, padded, padded, off, ln, n_bins=ctx_big.n_bins, qual_offsets=qoff)
+        assert s["n_records"] == len(reads) and np.array_equal(idx.seq_off, off) and np.array_equal(idx.qual_off, qoff)
+        records_equal(r, f, exp_r, exp_f, "the text object after the refusal")
+        assert_tallies(ctx_big, exp, "the text object after the refusal")
+    finally:
+        tx.close()
+        ctx.close()
+        ctx_big.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -25,6 +25,11 @@ def test_emul_host_side_refusals_leave_the_context_alone(emul):
     refusals.host_refusals(emul)
 
 
+def test_emul_text_larger_than_the_context_takes(emul):
+    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "Makefile.text"], check=True)
+    refusals.text_over_capacity(emul, os.path.join(EMUL_DIR, "libtgsf_text_emul.so"))
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("at", [0, 7, 256, -1])
 @pytest.mark.parametrize("kind", ["len0", "offsets", "over"])

@@ -14,6 +14,10 @@ def test_gpu_host_side_refusals_leave_the_context_alone():
     refusals.host_refusals(None)
 
 
+def test_gpu_text_larger_than_the_context_takes():
+    refusals.text_over_capacity(None, None)
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("at", [0, 7, 256, -1])
 @pytest.mark.parametrize("kind", ["len0", "offsets", "over"])

@@ -53,7 +53,7 @@ struct tgsf_ctx {
     bool own_stream;
     std::string error;
     // capacities
-    uint64_t cap_bases;
+    uint64_t cap_bases, cap_chunks;      // cap_chunks: the most chunks of the middle scan a batch of the accepted span can have (tgsf_create)
     uint32_t cap_reads, max_read_len, n_bins;
     static constexpr unsigned endtab_grid = 512;   // k_end_tables: LDS-atomic bound, 40 KB of LDS per block: two blocks per CU (128: 0.36 ms, 512: 0.19 ms)
     static constexpr unsigned stats_grid = 768;    // k_stats: 3 blocks (12 waves) per CU on 256 CUs, LDS-limited
@@ -532,18 +532,23 @@ extern "C" int tgsf_create(const tgsf_params* p, int device, tgsf_ctx** out)
     if (!e) e = dev_alloc(c, &B.pool_n, 4);
     if (!e) e = dev_alloc(c, &B.seg_cnt, n + 1);
     if (!e) e = dev_alloc(c, &B.chk_cnt, n + 1);
-    if (c->cap_bases / 16u + n >= 0xFFFFFFF0ull) c->flat_scan = false;   // (chunk numbers are 32 bits: such a context keeps k_mid_scan1)
-    if (c->cap_bases / 16u + n >= (1ull << 30) || !c->flat_scan) c->suffix_filter = 0;   // (k_mid_recheck's items: a chunk number and two bits)
+    // The chunks of a batch (16 columns of a read's middle window, counted from the window's start: k_gate_reads) number at
+    // most span / 16 + reads, and the largest span a submit accepts is cap_bases + 16 * cap_reads -- all of which may be
+    // bases: a batch of unpadded reads is held to the span alone.
+    const uint64_t cap_chunks = c->cap_bases / 16u + 2ull * n;
+    c->cap_chunks = cap_chunks;
+    if (cap_chunks >= 0xFFFFFFF0ull) c->flat_scan = false;   // (chunk numbers are 32 bits: such a context keeps k_mid_scan1)
+    if (cap_chunks >= (1ull << 30) || !c->flat_scan) c->suffix_filter = 0;   // (k_mid_recheck's items: a chunk number and two bits)
     {
         // (no adapter the filter takes -- the ONT rapid adapters at the default -M, k = 16 --: none of its buffers either)
         bool any = false;
         for (int a = 0; a < p->n_adapters; a++) any |= c->P.Q[a] > 32 && c->P.Q[a] <= 64 && c->P.k_mid[a] >= 0 && c->P.k_mid[a] <= kSuffixMaxK;
         if (!any || !p->filter) c->suffix_filter = 0;
     }
-    if (!e && c->suffix_filter) e = dev_alloc(c, &B.chk_mark, (size_t)4 * (size_t)((c->cap_bases / 16u + n) / 32u + 8u));
+    if (!e && c->suffix_filter) e = dev_alloc(c, &B.chk_mark, (size_t)4 * (size_t)(cap_chunks / 32u + 8u));
     if (c->suffix_filter) {
         // a mark in 25 chunks has room in the list (random sequence: a few in a thousand), the rest is done where it is found
-        B.rc_cap = (uint32_t)std::min<uint64_t>((c->cap_bases / 16u + n) / 25u + 4096u, 1ull << 24);
+        B.rc_cap = (uint32_t)std::min<uint64_t>(cap_chunks / 25u + 4096u, 1ull << 24);
         if (const char* e2 = knob("TGSF_RECHECK_CAP")) { int v = atoi(e2); if (v >= 0) B.rc_cap = (uint32_t)v; }   // test knob
         if (!e) e = dev_alloc(c, &B.rc_list, (size_t)B.rc_cap + 1);
         if (!e) e = dev_alloc(c, &B.rc_n, 4);
@@ -551,7 +556,7 @@ extern "C" int tgsf_create(const tgsf_params* p, int device, tgsf_ctx** out)
     if (!e) e = dev_alloc(c, &B.nfr, n + 1);
     if (!e) e = dev_alloc(c, &B.scan_part, n / kScanTile + 2);
     if (!e) e = dev_alloc(c, &B.trimmed, n);
-    B.rep_long_cap = (uint32_t)std::min<uint64_t>(c->cap_bases / kRepShare + 16, (uint64_t)B.fcap + 16);   // a long fragment holds more than kRepShare bases
+    B.rep_long_cap = (uint32_t)std::min<uint64_t>((c->cap_bases + 16ull * n) / kRepShare + 16, (uint64_t)B.fcap + 16);   // a long fragment holds more than kRepShare bases
     if (!e) e = dev_alloc(c, &B.rep_next, 2 + (size_t)B.rep_long_cap);
     if (p->min_repeat > 0 && p->kmer >= 12 && p->kmer <= 31) {
         // k_repeat_keys' last resort: room for the set of all k-mers of the longest fragment, half empty
@@ -806,7 +811,7 @@ static int run_pipeline(tgsf_ctx* c, const tgsf_batch_in* in, tgsf_read_result* 
             if (flat) {
                 scan_u32(B, B.chk_cnt, n, st);
                 FlatSchedule S;
-                const uint64_t tb = std::min<uint64_t>(in->n_bytes / 16u + (uint64_t)n, c->cap_bases / 16u + c->cap_reads);
+                const uint64_t tb = std::min<uint64_t>(in->n_bytes / 16u + (uint64_t)n, c->cap_chunks);
                 flat_chunks = tb;
                 flat_schedule((uint32_t)tb, B.flat_pmax, B.flat_pmin, B.flat_f0, S);
                 // The batch's real chunk count T' <= tb is on the device.  The number of stretches is not monotonic in it: a group
@@ -1166,6 +1171,9 @@ extern "C" int tgsf_submit_device(tgsf_ctx* c, const tgsf_batch_in* in, tgsf_bat
     if (e) return e;
     if (!out || !out->reads) return fail(c, TGSF_E_INVALID, "null output");
     if (((uintptr_t)in->seq & 15u) || (!c->P.no_qual && ((uintptr_t)in->qual & 15u))) return fail(c, TGSF_E_INVALID, "seq/qual device pointers must be 16-byte aligned");
+    // the span sizes launches and is the bound of every per-chunk buffer: the offsets are on the device, so it cannot be derived here
+    if (!in->n_bytes) return fail(c, TGSF_E_INVALID, "n_bytes is 0: a device batch must state the bytes it spans");
+    if (in->n_bytes > c->cap_bases + 16ull * c->cap_reads) return fail(c, TGSF_E_CAPACITY, "batch spans %llu bytes, context was sized for %llu bases", (unsigned long long)in->n_bytes, (unsigned long long)c->cap_bases);
 #if !defined(TGSF_EMUL)
     (void)hipSetDevice(c->device);
 #endif
