@@ -122,6 +122,12 @@ CASES.update({
                       "-x ont -l 1000 -q 7 -5 0 -3 2 -M 1200 -m 900 -E 2600 -T 40", "fq", "giant"),
 })
 
+CASES.update({
+    # every byte value a FASTQ line can carry in bases and qualities (tests/bytes_domain.py, odd_bytes_into): the case fold, bit 7,
+    # the signed quality - qType and the exact-byte equality of edlib, through the reference's whole program
+    "odd_bytes": (dict(seed=41, n=60, kind="ont", mean_len=2500, zoo=True, pmid=0.1), [synth.ONT_RAPID], "-x ont -l 500 -q 7 -5 7 -3 8 -e 200", "fq", "odd_bytes"),
+})
+
 IN_EXT = {"fq": "in.fq", "bam": "in.bam", "sam": "in.sam", "fa": "in.fa"}
 
 
@@ -144,6 +150,9 @@ def tweak(reads, how):
                 sq[pos:pos + len(m)] = m
             out.append((name, bytes(sq), q))
         return out
+    if how == "odd_bytes":
+        from tests import bytes_domain
+        return bytes_domain.odd_bytes_into(reads, 41)
     for i, (name, sq, q) in enumerate(reads):
         if how == "phred64":
             q = bytes(min(max(c, 33 + 16) + 31, 126) for c in q)     # every quality >= 16: min char 80 > 78 decides Phred64 (:1050)

@@ -240,6 +240,17 @@ def _kmer_repeat_np(seq: bytes, k: int) -> int:
     return int(total - np.unique(km).size)
 
 
+def _kmer_repeat_k32(seq: bytes) -> int:
+    """GetKmerCount at k = 32 as the reference binary does it (oracle/tgsf_oracle.c, kmer_repeat; goldens repeat_k32 / repeat_k32b):
+    the first k-mer goes in as built, every later one is masked to 0."""
+    a = np.frombuffer(seq, dtype=np.uint8)
+    total = a.size - 32 + 1
+    if total <= 0:
+        return 0
+    first_is_zero = not np.isin(a[:32], np.frombuffer(b"CGT", dtype=np.uint8)).any()
+    return total - (1 if total == 1 or first_is_zero else 2)
+
+
 REPEAT_TINY = [100, 101, 111, 112, 113, 127, 128, 129, 130, 143, 144, 145]
 REPEAT_SHORT = [500, 1000, 1023, 1024, 1025, 4097, 16384, 20000]
 _W = 6 * 1024 * 16      # bases of k_repeat's window (one 16-base chunk is shared between consecutive windows)
@@ -278,7 +289,7 @@ def repeat_threshold_case(lib_path, k, lens, max_runs=64, alphabet=b"ACGT", shar
             body[int(pos)] = int(np.frombuffer(b"Nacgt", dtype=np.uint8)[rng.integers(0, 5)])
         q = bytes((rng.integers(12, 30, L) + 33).astype(np.uint8))
         reads.append((b"r%d_%s" % (L, b"x" * int(rng.integers(0, 16))), body.tobytes(), q))
-        counts.append(_kmer_repeat_np(body.tobytes(), k))
+        counts.append(_kmer_repeat_np(body.tobytes(), k) if k < 32 else _kmer_repeat_k32(body.tobytes()))
     counts = np.array(counts)
     thresholds = sorted({int(c) + d for c in counts for d in (0, 1) if int(c) + d > 0})
     if len(thresholds) > max_runs:
@@ -577,20 +588,33 @@ def async_two_contexts(lib_path):
         c.close()
 
 
-def align_windows_random(lib_path, n, seed=9, golden_dir=None, lengths=None, max_window=400, plant_whole=False):
+def align_windows_random(lib_path, n, seed=9, golden_dir=None, lengths=None, max_window=400, plant_whole=False,
+                         adapters=None, alphabet=None, mutate=None):
     """tgsf_align_windows against edlib itself where oracle/_ref/libedlib_ref.so exists (compiled from the
     reference's include/edlib.cpp), else against the oracle's DP restatement: random adapters of 20..256 bp,
-    windows of 5..400 bp with planted mutated copies, homopolymers and Ns, assorted k."""
+    windows of 5..400 bp with planted mutated copies, homopolymers and Ns, assorted k.
+    adapters: these instead (any bytes; one beyond 256 bp makes the context a wide one); alphabet: the bytes the windows
+    are drawn from instead of ACGT; mutate: instead of synth.mutate (tests/bytes_domain.py: replacements from all 256
+    values).  Without the three the cases are what they have always been."""
     import ctypes as C
     ref_so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libedlib_ref.so")
     rng = np.random.default_rng(seed)
-    acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
-    adapters = [synth.ONT_RAPID, synth.PACBIO_BLUNT, b"AATGTACTTCGTTCAGTTACGTATTGCT", b"GCAATACGTAACTGAACGAAGT"]
-    adapters += [bytes(acgt[rng.integers(0, 4, int(L))]) for L in (lengths or (20, 33, 64, 65, 90, 127, 128, 129, 150, 192, 193, 230, 256))]
-    if lengths:                                   # (adapters beyond 256 bp: the wide path; a few short ones ride along)
-        adapters = adapters[4:] + adapters[:2]
-    p = abi.make_params("ont", adapters=adapters, max_batch_bases=1 << 22, max_batch_reads=4096 if not lengths else (256 if max_window <= 2600 else 16), max_read_len=4096,
-                        **({"mid_match_len": 1, "end_match_len": 1} if lengths else {}))
+    acgt = np.frombuffer(b"ACGT" if alphabet is None else bytes(alphabet), dtype=np.uint8)
+    nsym = len(acgt)
+    mutate = mutate or synth.mutate
+    if adapters is None:
+        adapters = [synth.ONT_RAPID, synth.PACBIO_BLUNT, b"AATGTACTTCGTTCAGTTACGTATTGCT", b"GCAATACGTAACTGAACGAAGT"]
+        adapters += [bytes(acgt[rng.integers(0, 4, int(L))]) for L in (lengths or (20, 33, 64, 65, 90, 127, 128, 129, 150, 192, 193, 230, 256))]
+        if lengths:                                   # (adapters beyond 256 bp: the wide path; a few short ones ride along)
+            adapters = adapters[4:] + adapters[:2]
+        wide = bool(lengths)
+        cap = 4096 if not lengths else (256 if max_window <= 2600 else 16)
+    else:
+        adapters = [bytes(a) for a in adapters]
+        wide = any(len(a) > 256 for a in adapters)
+        cap = max(256, n)
+    p = abi.make_params("ont", adapters=adapters, max_batch_bases=1 << 22, max_batch_reads=cap, max_read_len=4096,
+                        **({"mid_match_len": 1, "end_match_len": 1} if wide else {}))
     ctx = capi.Context(p, 0, lib_path)
     buf, off, ln, aid, ks, trip = bytearray(), [], [], [], [], []
     for i in range(n):
@@ -598,17 +622,17 @@ def align_windows_random(lib_path, n, seed=9, golden_dir=None, lengths=None, max
         q = adapters[a]
         Q = len(q)
         T = int(rng.integers(5, 40)) if i % 9 == 0 else int(rng.integers(40, max_window))
-        t = bytearray(acgt[rng.integers(0, 4, T)].tobytes())
+        t = bytearray(acgt[rng.integers(0, nsym, T)].tobytes())
         if i % 11 == 5:
             t = bytearray(b"T" * T)
         if plant_whole:                            # a whole (mutated) copy in a window that holds it: the path spans ~Q columns
             T = int(rng.integers(Q // 2, min(max_window, 2 * Q + 200)))
-            t = bytearray(acgt[rng.integers(0, 4, T)].tobytes())
+            t = bytearray(acgt[rng.integers(0, nsym, T)].tobytes())
         for _ in range(int(rng.integers(0, 3)) if not plant_whole else 1):
-            m = synth.mutate(rng, q, float(rng.choice([0.0, 0.05, 0.15, 0.3])))
+            m = mutate(rng, q, float(rng.choice([0.0, 0.05, 0.15, 0.3])))
             if plant_whole and rng.random() < 0.3:   # ... with a long stretch of other text in its middle
                 h = len(m) // 2
-                m = m[:h] + bytes(acgt[rng.integers(0, 4, int(rng.integers(1, 400)))]) + m[h:]
+                m = m[:h] + bytes(acgt[rng.integers(0, nsym, int(rng.integers(1, 400)))]) + m[h:]
             if rng.random() < 0.3 and not plant_whole:
                 m = m[int(rng.integers(0, len(m))):]
             pos = int(rng.integers(0, T))

@@ -26,7 +26,7 @@ def test_emul_edlib_vectors(emul, golden_dir):
     parity.edlib_vectors(emul, golden_dir)
 
 
-@pytest.mark.parametrize("name", ["ont_zoo", "ont_trim", "ont_discard", "hifi_zoo", "long_adapter", "qc_only", "ont_m1", "huge_adapter", "ont_phred64", "ont_e1300", "wide_adapter"])
+@pytest.mark.parametrize("name", ["ont_zoo", "ont_trim", "ont_discard", "hifi_zoo", "long_adapter", "qc_only", "ont_m1", "huge_adapter", "ont_phred64", "ont_e1300", "wide_adapter", "odd_bytes"])
 def test_emul_golden(emul, golden_dir, name):
     parity.golden_case(emul, golden_dir, name)
 
