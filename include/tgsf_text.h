@@ -27,6 +27,9 @@
  *
  * Multi-line FASTA is not read by the reference either: the rule stops there.
  *
+ * THE OUTPUT SIDE (tgsf_text_format*, tgsf_text_filter, further down): the records the filter kept, formatted as clean
+ * FASTQ / FASTA text on the device, from the text, the index and the filter's fragment table, all of which sit in HBM already.
+ *
  * Conventions as in tgsf.h: plain C, 0 or a negative tgsf_status; calls on one object are serialised by the caller,
  * different objects may be driven from different threads.  No CPU fallback.
  */
@@ -39,7 +42,7 @@
 extern "C" {
 #endif
 
-#define TGSF_TEXT_ABI_VERSION 1
+#define TGSF_TEXT_ABI_VERSION 2
 #define TGSF_TEXT_PAD 64u  /* bytes of zeros the object keeps behind the text in its own buffer */
 
 /* why the index ends where it ends */
@@ -144,6 +147,90 @@ int tgsf_text_fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf
  */
 int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
                      const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* batch_out);
+
+/*
+ * ---- the output side: text in, clean text out -------------------------------------------------------------------------
+ *
+ * THE RULE (tgsfilter_amd/host/record_out.h; the reference's record formatting, src/TGSFilter.cpp:2011-2053, and newSeqName,
+ * :1680-1701).  The output is the concatenation, in the order of the fragment table, of one record per fragment with
+ * TGSF_FF_PASS:
+ *
+ *     '@' (fastq_out) or '>'   name'   '\n'   text[seq_off[read] + start .. + len)
+ *                              [ "\n+\n"   text[qual_off[read] + start .. + len) ]   (fastq_out only)   '\n'
+ *
+ * name = text[name_off[read] .. + name_len[read]).  pass_num is 1 for the read's first fragment with TGSF_FF_PASS, 2 for
+ * its second and so on (other fragments do not count); name' = name for pass_num 1, else ":" and pass_num in decimal are
+ * inserted in front of the first byte of name that is one of " \t\n\v\f\r" (an interior '\r' counts), or appended
+ * where there is none.  An empty name is allowed ("@:2\n").  Line ends are '\n' whatever the input used.
+ *
+ * THE TABLES ARE TRUSTED, as tgsf.h trusts offsets: `reads` has n_records entries whose frag_begin is the index of the
+ * read's first fragment in `frags`; the fragments are in the order of their reads (what tgsf_batch_out holds); every
+ * fragment has read < n_records, start >= 0 and start + len <= len[read].  This is THE CALLER'S DUTY: the library does not
+ * check it, and a table that breaks it makes the kernels read outside the text.
+ */
+
+/* 32 bytes */
+typedef struct tgsf_text_out_summary {
+    uint64_t n_bytes;      /* bytes of the formatted text; with TGSF_TEXT_CAPACITY the size that is needed          */
+    uint64_t bases;        /* sum of len over the records                                                           */
+    uint32_t n_records;    /* records of the output: fragments with TGSF_FF_PASS                                    */
+    uint32_t stop;         /* TGSF_TEXT_END: everything was written.  TGSF_TEXT_CAPACITY: n_bytes > out_capacity and
+                              NOTHING was written to the output (nor to rec_end)                                    */
+    float    device_ms;    /* the output kernels by HIP events, when tgsf_text_profile is on and the call synchronises
+                              (tgsf_text_format, tgsf_text_filter); else 0                                          */
+    uint32_t reserved;
+} tgsf_text_out_summary;
+
+/*
+ * Once, before the first format: per-fragment scratch for up to max_frags fragments a call, the object's own output
+ * buffer of max_out_bytes bytes (16-byte aligned) and fragment records on the device.  No later call allocates.
+ * A format call before it is TGSF_E_INVALID, one with n_frags > max_frags TGSF_E_CAPACITY, both before anything is
+ * enqueued; the object stays usable.  A second call is TGSF_E_INVALID.
+ */
+int tgsf_text_out_reserve(tgsf_text* tx, uint32_t max_frags, uint64_t max_out_bytes);
+
+/*
+ * Everything in HBM; the kernels are enqueued on `hip_stream` (NULL: the object's own stream) and nothing is waited for.
+ * d_text / d_index NULL: the object's own buffer and arrays, as tgsf_text_index_device left them.  d_reads (n_records
+ * entries) and d_frags (n_frags entries) are the filter's results on the device; n_records and n_frags are host values
+ * (the caller has them after tgsf_wait).  fasta: what the index was made with; fastq_out with fasta = 1 is
+ * TGSF_E_INVALID (there are no qualities: qual_off == seq_off, which the device cannot tell from a FASTQ index).
+ * d_out NULL: the object's own output buffer (out_capacity above max_out_bytes is then cut to it); a caller's d_out
+ * must be 16-byte aligned.  No byte at or behind n_bytes is written, none at or behind out_capacity.
+ * d_rec_end (optional; room for n_frags entries): entry i becomes the byte behind output record i.
+ * d_summary NULL: the object's own.  The scratch is the object's: one call at a time, or all on one stream.
+ */
+int tgsf_text_format_device(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_index_arrays* d_index, uint32_t n_records,
+                            int fasta, const tgsf_read_result* d_reads, const tgsf_fragment* d_frags, uint32_t n_frags,
+                            int fastq_out, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_rec_end,
+                            tgsf_text_out_summary* d_summary, void* hip_stream);
+
+/*
+ * The same with HOST tables and a HOST output buffer, for the text and the index that are in the object (after
+ * tgsf_text_upload + tgsf_text_index_device, tgsf_text_index or tgsf_text_submit): the tables go up, the text is
+ * formatted into the object's output buffer, the summary and n_bytes bytes come down (and n_records entries of rec_end,
+ * which may be NULL).  With TGSF_TEXT_CAPACITY only the summary comes down and the call returns TGSF_E_CAPACITY;
+ * out_summary->n_bytes says what is needed (of out_capacity, or of tgsf_text_out_reserve's max_out_bytes).
+ */
+int tgsf_text_format(tgsf_text* tx, uint32_t n_records, int fasta, const tgsf_read_result* reads, const tgsf_fragment* frags,
+                     uint32_t n_frags, int fastq_out, uint8_t* out, uint64_t out_capacity, uint64_t* rec_end,
+                     tgsf_text_out_summary* out_summary);
+
+/*
+ * Text in, clean text out: exactly tgsf_text_submit (its refusals are handed through unchanged), then the regular
+ * prefix's kept records formatted on the device and one copy down (rec_end as for tgsf_text_format; may be NULL).  batch_out may be NULL: the per-read records and the
+ * fragments then stay on the device, in the object's scratch (at most max_frags fragments); with batch_out they come
+ * down too, as from tgsf_text_submit.  out_index may be NULL.  n_records == 0: nothing runs, out_summary->n_bytes = 0,
+ * no error.  Only the regular prefix is filtered: look at in_summary->stop and ->consumed.
+ */
+int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
+                     uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                     tgsf_text_summary* in_summary,
+                     const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out);
+
+/* Milliseconds of the last format's three stages -- sizes (flags, their sums, sizes), layout (the sums of the sizes, the
+ * record ends), copy -- when tgsf_text_profile was on; waits for that format to finish. */
+int tgsf_text_out_stage_ms(tgsf_text* tx, float ms[3]);
 
 #ifdef __cplusplus
 }

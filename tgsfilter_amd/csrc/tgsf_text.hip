@@ -59,10 +59,27 @@ struct tgsf_text {
     tgsf_fragment* d_frags = nullptr;
     uint32_t frag_cap = 0;
     uint32_t* d_nfrags = nullptr;
+    // the output side (tgsf_text_out_reserve): per-fragment scratch, the object's own output buffer
+    bool out_reserved = false;
+    uint32_t max_frags = 0;
+    uint64_t max_out = 0;
+    uint32_t* d_opass = nullptr;        // PASS flags -> exclusive sums within blocks of kTextScanTile fragments
+    uint64_t* d_opass_part = nullptr;   // ... and the blocks' offsets
+    uint64_t* d_osize = nullptr;        // record sizes -> the same, 64-bit
+    uint64_t* d_osize_part = nullptr;
+    uint64_t* d_oends = nullptr;        // the byte behind each fragment's record
+    TextOutMeta* d_ometa = nullptr;
+    TextOutState* d_ostate = nullptr;
+    tgsf_fragment* d_ofrags = nullptr;  // fragment records: tgsf_text_format's table, tgsf_text_filter without batch_out
+    uint64_t* d_orec_end = nullptr;
+    uint8_t* d_out = nullptr;
+    tgsf_text_out_summary* d_osummary = nullptr;
     std::vector<void*> allocs;
 #if !defined(TGSF_EMUL)
     hipEvent_t ev[2] = {nullptr, nullptr};
     bool ev_recorded = false;
+    hipEvent_t oev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool oev_recorded = false;
 #endif
 };
 
@@ -98,6 +115,7 @@ extern "C" void tgsf_text_destroy(tgsf_text* tx)
     (void)hipSetDevice(tx->device);
     if (tx->stream) { (void)hipStreamSynchronize(tx->stream); (void)hipStreamDestroy(tx->stream); }
     for (hipEvent_t e : tx->ev) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : tx->oev) if (e) (void)hipEventDestroy(e);
 #endif
     for (void* p : tx->allocs) rt_free(p);
     delete tx;
@@ -308,28 +326,20 @@ extern "C" int tgsf_text_index(tgsf_text* tx, const uint8_t* text, uint64_t n_by
     return fetch(tx, out_index, out_summary, &sum);
 }
 
-extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
-                                const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo)
+// tgsf_text_submit; bo == NULL (tgsf_text_filter only): nothing but the summary comes down.  The fragments go to d_fr on the
+// device (room for fr_cap; NULL: not wanted), their number to *n_frags.
+static int submit_core(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
+                       const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo,
+                       tgsf_fragment* d_fr, uint32_t fr_cap, uint32_t* n_frags)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_args(tx, n_bytes, fasta, final);
-    if (e) return e;
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
-    if (bo->frags && bo->frag_capacity > tx->frag_cap) {               // fragment records on the device: as many as the caller takes
-        tgsf_fragment* f = nullptr;
-        if (dev_alloc(tx, &f, bo->frag_capacity)) return fail(tx, TGSF_E_HIP, "device allocation failed (%u fragment records)", bo->frag_capacity);
-        tx->d_frags = f;                                               // (the smaller one stays allocated until destroy)
-        tx->frag_cap = bo->frag_capacity;
-    }
+    int e;
     if ((e = upload(tx, text, n_bytes))) return e;
     if ((e = enqueue_index(tx, tx->d_text, n_bytes, fasta, final, tx->d_index, tx->d_summary, tx->stream))) return e;
     tgsf_text_summary sum;
     // the one wait between the index and the filter: libtgsf sizes its launches by n_reads on the host
     if ((e = fetch(tx, nullptr, nullptr, &sum))) return e;
-    bo->n_frags = 0;
+    if (bo) bo->n_frags = 0;
+    *n_frags = 0;
     if (sum.n_records) {
         tgsf_batch_in in;
         memset(&in, 0, sizeof in);
@@ -342,27 +352,263 @@ extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* tex
         in.n_bytes = n_bytes;
         tgsf_batch_out dout;
         dout.reads = tx->d_reads;
-        dout.frags = bo->frags ? tx->d_frags : nullptr;
-        dout.frag_capacity = bo->frags ? bo->frag_capacity : 0u;
+        dout.frags = d_fr;
+        dout.frag_capacity = d_fr ? fr_cap : 0u;
         dout.n_frags = 0;
         e = tgsf_submit_device(ctx, &in, &dout, tx->d_nfrags, (void*)tx->stream);
         if (!e) e = tgsf_wait(ctx);
         if (e) return fail(tx, e, "libtgsf: %s", tgsf_last_error(ctx));
         uint32_t nf = 0;
         int he = rt_d2h(&nf, tx->d_nfrags, 4, tx->stream);
-        he |= rt_d2h(bo->reads, tx->d_reads, (size_t)sum.n_records * sizeof(tgsf_read_result), tx->stream);
+        if (bo) he |= rt_d2h(bo->reads, tx->d_reads, (size_t)sum.n_records * sizeof(tgsf_read_result), tx->stream);
         if (!he) he = rt_sync(tx->stream);
         if (!he && nf > dout.frag_capacity) return fail(tx, TGSF_E_CAPACITY, "batch produced %u fragments, caller provided room for %u", nf, dout.frag_capacity);
-        if (!he && nf) {
-            he = rt_d2h(bo->frags, tx->d_frags, (size_t)nf * sizeof(tgsf_fragment), tx->stream);
+        if (!he && nf && bo && bo->frags) {
+            he = rt_d2h(bo->frags, d_fr, (size_t)nf * sizeof(tgsf_fragment), tx->stream);
             if (!he) he = rt_sync(tx->stream);
         }
         if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-        bo->n_frags = nf;
+        if (bo) bo->n_frags = nf;
+        *n_frags = nf;
     }
     // the index last: the filter does not wait for it
     tgsf_text_summary again;
     if (out_index && (e = fetch(tx, out_index, nullptr, &again))) return e;
     *out_summary = sum;
     return TGSF_OK;
+}
+
+// fragment records on the device for a caller who takes them: as many as the caller takes
+static int grow_frags(tgsf_text* tx, const tgsf_batch_out* bo)
+{
+    if (bo->frags && bo->frag_capacity > tx->frag_cap) {
+        tgsf_fragment* f = nullptr;
+        if (dev_alloc(tx, &f, bo->frag_capacity)) return fail(tx, TGSF_E_HIP, "device allocation failed (%u fragment records)", bo->frag_capacity);
+        tx->d_frags = f;                                               // (the smaller one stays allocated until destroy)
+        tx->frag_cap = bo->frag_capacity;
+    }
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
+                                const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    if ((e = grow_frags(tx, bo))) return e;
+    uint32_t nf = 0;
+    return submit_core(tx, ctx, text, n_bytes, fasta, final, out_index, out_summary, bo, bo->frags ? tx->d_frags : nullptr,
+                       bo->frags ? bo->frag_capacity : 0u, &nf);
+}
+
+// ---- the output side ---------------------------------------------------------------------------------------------------
+extern "C" int tgsf_text_out_reserve(tgsf_text* tx, uint32_t max_frags, uint64_t max_out_bytes)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (tx->out_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_out_reserve has been called already (%u fragments, %llu bytes)", tx->max_frags, (unsigned long long)tx->max_out);
+    if (max_frags == 0 || max_out_bytes == 0) return fail(tx, TGSF_E_INVALID, "max_frags and max_out_bytes must be positive");
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+    for (hipEvent_t& ev : tx->oev) if (!ev && hipEventCreate(&ev) != hipSuccess) return fail(tx, TGSF_E_HIP, "event creation failed");
+#endif
+    const size_t parts = (size_t)max_frags / kTextScanTile + 2;
+    int e = 0;
+    e |= dev_alloc(tx, &tx->d_out, ((max_out_bytes + 15u) & ~15ull));
+    if (!e) e |= dev_alloc(tx, &tx->d_opass, max_frags);
+    if (!e) e |= dev_alloc(tx, &tx->d_opass_part, parts);
+    if (!e) e |= dev_alloc(tx, &tx->d_osize, max_frags);
+    if (!e) e |= dev_alloc(tx, &tx->d_osize_part, parts);
+    if (!e) e |= dev_alloc(tx, &tx->d_oends, max_frags);
+    if (!e) e |= dev_alloc(tx, &tx->d_ometa, max_frags);
+    if (!e) e |= dev_alloc(tx, &tx->d_ostate, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_ofrags, max_frags);
+    if (!e) e |= dev_alloc(tx, &tx->d_orec_end, max_frags);
+    if (!e) e |= dev_alloc(tx, &tx->d_osummary, 1);
+    if (e) return fail(tx, TGSF_E_HIP, "device allocation failed (%u fragments, %llu bytes of output)", max_frags, (unsigned long long)max_out_bytes);
+    tx->max_frags = max_frags;
+    tx->max_out = max_out_bytes;
+    tx->out_reserved = true;
+    return TGSF_OK;
+}
+
+// what every format call is refused for before anything is enqueued
+static int check_format(tgsf_text* tx, uint32_t n_frags, int fasta, int fastq_out)
+{
+    if (!tx->out_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_out_reserve has not been called on this object: no scratch to format with");
+    if (n_frags > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", n_frags, tx->max_frags);
+    if ((fasta != 0 && fasta != 1) || (fastq_out != 0 && fastq_out != 1)) return fail(tx, TGSF_E_INVALID, "fasta and fastq_out are 0 or 1");
+    if (fasta && fastq_out) return fail(tx, TGSF_E_INVALID, "FASTQ output from a FASTA index: the records have no qualities");
+    return TGSF_OK;
+}
+
+// the launches of one format, on st; nothing is waited for
+static int enqueue_format(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_index_arrays& I, const tgsf_read_result* d_reads,
+                          const tgsf_fragment* d_frags, uint32_t n_frags, int fastq_out, uint8_t* d_out, uint64_t capacity,
+                          uint64_t* d_rec_end, tgsf_text_out_summary* d_summary, rt_stream st)
+{
+    const uint64_t n = n_frags;
+    const uint32_t nb = (uint32_t)((n + kTextScanTile - 1) / kTextScanTile);
+    const unsigned gfrag = grid_cap(std::min(std::max(blocks_for(n, kTextThreads), 1u), 2048u));
+    // a wave per 4 KiB piece of the output, as many as the capacity has, at most a few per SIMD of the device: they stride
+    const unsigned gcopy = grid_cap(std::min(std::max(blocks_for(((capacity + kTextPiece - 1) / kTextPiece) * kTextLanes, kTextThreads), 1u), 2048u));
+    TextOutState* S = tx->d_ostate;
+#if !defined(TGSF_EMUL)
+    if (tx->profile) { (void)hipEventRecord(tx->oev[0], st); }
+#endif
+    TGSF_LAUNCH(k_textout_flag, gfrag, kTextThreads, st, d_frags, n, tx->d_opass, S);
+    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles, nb, 256, st, tx->d_opass, n, tx->d_opass_part);
+    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_opass_part, nb, &S->n_records);
+    if (n) {
+        TGSF_LAUNCH(k_textout_size, gfrag, kTextThreads, st, d_text, I, d_reads, d_frags, n, fastq_out, (const uint32_t*)tx->d_opass,
+                    (const uint64_t*)tx->d_opass_part, tx->d_osize, tx->d_ometa, S);
+#if !defined(TGSF_EMUL)
+        if (tx->profile) { (void)hipEventRecord(tx->oev[1], st); }
+#endif
+        TGSF_LAUNCH_COOP(k_textout_scan_tiles64, nb, 256, st, tx->d_osize, n, tx->d_osize_part);
+    }
+#if !defined(TGSF_EMUL)
+    else if (tx->profile) { (void)hipEventRecord(tx->oev[1], st); }
+#endif
+    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_osize_part, nb, &S->n_bytes);
+    TGSF_LAUNCH(k_textout_finish, gfrag, kTextThreads, st, (const uint64_t*)tx->d_osize, (const uint64_t*)tx->d_osize_part,
+                (const uint32_t*)tx->d_opass, (const uint64_t*)tx->d_opass_part, (const TextOutMeta*)tx->d_ometa, n, capacity,
+                (const TextOutState*)S, tx->d_oends, d_rec_end, d_summary);
+#if !defined(TGSF_EMUL)
+    if (tx->profile) { (void)hipEventRecord(tx->oev[2], st); }
+#endif
+    if (n)
+        TGSF_LAUNCH(k_textout_copy, gcopy, kTextThreads, st, d_text, I, d_frags, (const TextOutMeta*)tx->d_ometa, (const uint64_t*)tx->d_oends,
+                    n, fastq_out, (const TextOutState*)S, capacity, d_out);
+#if !defined(TGSF_EMUL)
+    if (tx->profile) { (void)hipEventRecord(tx->oev[3], st); tx->oev_recorded = true; }
+    if (hipGetLastError() != hipSuccess) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+#endif
+    return TGSF_OK;
+}
+
+// milliseconds of the last format's stages; ms[3] (may be NULL); returns their sum.  The format has finished.
+static float format_ms(tgsf_text* tx, float* ms)
+{
+    float sum = 0.0f;
+    if (ms) ms[0] = ms[1] = ms[2] = 0.0f;
+#if !defined(TGSF_EMUL)
+    if (tx->profile && tx->oev_recorded) {
+        for (int k = 0; k < 3; k++) {
+            float t = 0.0f;
+            if (hipEventElapsedTime(&t, tx->oev[k], tx->oev[k + 1]) != hipSuccess) { (void)hipGetLastError(); return 0.0f; }
+            if (ms) ms[k] = t;
+            sum += t;
+        }
+    }
+#endif
+    (void)tx;
+    return sum;
+}
+
+extern "C" int tgsf_text_out_stage_ms(tgsf_text* tx, float ms[3])
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ms) return fail(tx, TGSF_E_INVALID, "null argument");
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+    if (tx->profile && tx->oev_recorded && hipEventSynchronize(tx->oev[3]) != hipSuccess) return fail(tx, TGSF_E_HIP, "waiting for the format failed");
+#endif
+    (void)format_ms(tx, ms);
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_format_device(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_index_arrays* d_index, uint32_t n_records,
+                                       int fasta, const tgsf_read_result* d_reads, const tgsf_fragment* d_frags, uint32_t n_frags,
+                                       int fastq_out, uint8_t* d_out, uint64_t out_capacity, uint64_t* d_rec_end,
+                                       tgsf_text_out_summary* d_summary, void* hip_stream)
+{
+    if (!tx) return TGSF_E_INVALID;
+    int e = check_format(tx, n_frags, fasta, fastq_out);
+    if (e) return e;
+    if (n_frags && (!d_reads || !d_frags || !n_records)) return fail(tx, TGSF_E_INVALID, "fragments without their table or without the per-read records");
+    if (d_index && (!d_index->seq_off || !d_index->qual_off || !d_index->len || !d_index->name_off || !d_index->name_len))
+        return fail(tx, TGSF_E_INVALID, "a device index needs all five arrays");
+    if (!d_index && n_records > tx->max_records)
+        return fail(tx, TGSF_E_CAPACITY, "%u records, the object's index arrays hold %u", n_records, tx->max_records);
+    if ((uintptr_t)d_out & 15u) return fail(tx, TGSF_E_INVALID, "the device output buffer must be 16-byte aligned");
+    if (!d_out) { d_out = tx->d_out; out_capacity = std::min(out_capacity, tx->max_out); }
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    return enqueue_format(tx, d_text ? d_text : tx->d_text, d_index ? *d_index : tx->d_index, d_reads, d_frags, n_frags, fastq_out, d_out,
+                          out_capacity, d_rec_end, d_summary ? d_summary : tx->d_osummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
+}
+
+// format what is on the device into the object's output buffer, on its stream; summary, text and record ends come down
+static int format_down(tgsf_text* tx, const tgsf_read_result* d_reads, const tgsf_fragment* d_frags, uint32_t n_frags, int fastq_out,
+                       uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary)
+{
+    const uint64_t cap = std::min(out_capacity, tx->max_out);
+    int e = enqueue_format(tx, tx->d_text, tx->d_index, d_reads, d_frags, n_frags, fastq_out, tx->d_out, cap, rec_end ? tx->d_orec_end : nullptr,
+                           tx->d_osummary, tx->stream);
+    if (e) return e;
+    tgsf_text_out_summary sum;
+    int he = rt_d2h(&sum, tx->d_osummary, sizeof sum, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    sum.device_ms = format_ms(tx, nullptr);
+    *out_summary = sum;
+    if (sum.stop == TGSF_TEXT_CAPACITY)
+        return fail(tx, TGSF_E_CAPACITY, "the formatted text has %llu bytes, there is room for %llu (out_capacity %llu, reserved %llu)",
+                    (unsigned long long)sum.n_bytes, (unsigned long long)cap, (unsigned long long)out_capacity, (unsigned long long)tx->max_out);
+    if (sum.n_bytes) he |= rt_d2h(out, tx->d_out, (size_t)sum.n_bytes, tx->stream);
+    if (rec_end && sum.n_records) he |= rt_d2h(rec_end, tx->d_orec_end, (size_t)sum.n_records * 8, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_format(tgsf_text* tx, uint32_t n_records, int fasta, const tgsf_read_result* reads, const tgsf_fragment* frags,
+                                uint32_t n_frags, int fastq_out, uint8_t* out, uint64_t out_capacity, uint64_t* rec_end,
+                                tgsf_text_out_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    int e = check_format(tx, n_frags, fasta, fastq_out);
+    if (e) return e;
+    if (!out_summary || (!out && out_capacity) || (n_frags && (!reads || !frags || !n_records))) return fail(tx, TGSF_E_INVALID, "null argument: summary, output buffer or tables");
+    if (n_records > tx->max_records) return fail(tx, TGSF_E_CAPACITY, "%u records, the object's index arrays hold %u", n_records, tx->max_records);
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    int he = 0;
+    if (n_frags) {
+        he |= rt_h2d(tx->d_reads, reads, (size_t)n_records * sizeof(tgsf_read_result), tx->stream);
+        he |= rt_h2d(tx->d_ofrags, frags, (size_t)n_frags * sizeof(tgsf_fragment), tx->stream);
+    }
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    return format_down(tx, tx->d_reads, tx->d_ofrags, n_frags, fastq_out, out, out_capacity, rec_end, out_summary);
+}
+
+extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
+                                uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                                tgsf_text_summary* in_summary,
+                                const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!text && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, fasta, fastq_out);
+    if (!e) e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+#if !defined(TGSF_EMUL)
+    (void)hipSetDevice(tx->device);
+#endif
+    const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts, as in tgsf_text_submit
+    if (down && (e = grow_frags(tx, bo))) return e;
+    tgsf_fragment* d_fr = down ? tx->d_frags : tx->d_ofrags;
+    uint32_t nf = 0;
+    memset(out_summary, 0, sizeof *out_summary);
+    if ((e = submit_core(tx, ctx, text, n_bytes, fasta, final, out_index, in_summary, bo, d_fr, down ? bo->frag_capacity : tx->max_frags, &nf))) return e;
+    if (!in_summary->n_records) return TGSF_OK;                        // nothing ran: an empty output, no error
+    if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
+    return format_down(tx, tx->d_reads, d_fr, nf, fastq_out, out, out_capacity, rec_end, out_summary);
 }

@@ -3,6 +3,8 @@
     tx = TextIndexer(0, max_bytes=len(text), max_records=100_000)
     idx, summary = tx.index(text)                       # five numpy arrays + the summary
     idx, summary, reads, frags = tx.submit(ctx, text)   # text in, filter results out (ctx: capi.Context)
+    tx.reserve_output(max_frags, max_out_bytes)         # once; then
+    clean, rec_end, out_summary, summary = tx.filter(ctx, text)   # text in, clean FASTQ / FASTA text out
 
 There is no CPU fallback: the library found beside this file must be the HIP build.  (tests/emul builds a serial
 emulation of the same kernels; only tests pass its path in.)
@@ -22,7 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "libtgsf_text.so")
 _LIBS = {}
 
-ABI_VERSION = 1
+ABI_VERSION = 2
 END, IRREGULAR, CAPACITY = 0, 1, 2
 STOP_NAMES = {END: "END", IRREGULAR: "IRREGULAR", CAPACITY: "CAPACITY"}
 PAD = 64
@@ -30,6 +32,7 @@ PAD = 64
 SYMBOLS = [
     "tgsf_text_abi_version", "tgsf_text_backend", "tgsf_text_create", "tgsf_text_destroy", "tgsf_text_last_error", "tgsf_text_profile",
     "tgsf_text_buffers", "tgsf_text_index", "tgsf_text_upload", "tgsf_text_index_device", "tgsf_text_fetch", "tgsf_text_submit",
+    "tgsf_text_out_reserve", "tgsf_text_format_device", "tgsf_text_format", "tgsf_text_filter", "tgsf_text_out_stage_ms",
 ]
 
 
@@ -51,7 +54,16 @@ class DeviceBuffers(C.Structure):
                 ("max_records", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class OutSummary(C.Structure):
+    _fields_ = [("n_bytes", C.c_uint64), ("bases", C.c_uint64), ("n_records", C.c_uint32), ("stop", C.c_uint32),
+                ("device_ms", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"n_bytes": self.n_bytes, "bases": self.bases, "n_records": self.n_records, "stop": self.stop, "device_ms": self.device_ms}
+
+
 assert C.sizeof(Summary) == 32
+assert C.sizeof(OutSummary) == 32
 
 Index = namedtuple("Index", "seq_off qual_off len name_off name_len")
 
@@ -80,6 +92,13 @@ def load(path: str | None = None):
         L.tgsf_text_index_device.argtypes = [vp, vp, u64, i, i, C.POINTER(IndexArrays), vp, vp]
         L.tgsf_text_fetch.argtypes = [vp, C.POINTER(IndexArrays), C.POINTER(Summary)]
         L.tgsf_text_submit.argtypes = [vp, vp, vp, u64, i, i, C.POINTER(IndexArrays), C.POINTER(Summary), C.POINTER(abi.BatchOut)]
+        u32 = C.c_uint32
+        L.tgsf_text_out_reserve.argtypes = [vp, u32, u64]
+        L.tgsf_text_format_device.argtypes = [vp, vp, C.POINTER(IndexArrays), u32, i, vp, vp, u32, i, vp, u64, vp, vp, vp]
+        L.tgsf_text_format.argtypes = [vp, u32, i, vp, vp, u32, i, vp, u64, vp, C.POINTER(OutSummary)]
+        L.tgsf_text_filter.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, C.POINTER(OutSummary), C.POINTER(Summary),
+                                       C.POINTER(IndexArrays), C.POINTER(abi.BatchOut)]
+        L.tgsf_text_out_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 3)]
         if L.tgsf_text_abi_version() != ABI_VERSION:
             raise RuntimeError("libtgsf_text ABI version mismatch")
         _LIBS[path] = L
@@ -185,3 +204,73 @@ class TextIndexer:
                                             C.byref(ia) if want_index else None, C.byref(s), C.byref(bo)))
         n = s.n_records
         return (self._clip(arrs, n) if want_index else None), s.as_dict(), reads[:n].copy(), frags[:bo.n_frags].copy()
+
+    # ---- the output side: the kept records as clean FASTQ / FASTA text ------------------------------------------------
+    def reserve_output(self, max_frags, max_out_bytes):
+        """Once, before the first format: scratch for max_frags fragments a call and an output buffer of max_out_bytes."""
+        self._chk(self.lib.tgsf_text_out_reserve(self.h, int(max_frags), int(max_out_bytes)))
+        self.max_frags, self.max_out_bytes = int(max_frags), int(max_out_bytes)
+
+    def _out(self, out, out_capacity):
+        """The host buffer a format writes into: the caller's (a writable uint8 array) or a new one of out_capacity bytes."""
+        if out is None:
+            out = np.empty(getattr(self, "max_out_bytes", 0) if out_capacity is None else int(out_capacity), np.uint8)
+        return out, (out.size if out_capacity is None else int(out_capacity))
+
+    def format(self, n_records, reads, frags, fastq_out=True, fasta=False, out=None, out_capacity=None):
+        """Format host tables (abi.READ_RESULT_DTYPE, abi.FRAGMENT_DTYPE) against the text and the index that are in the
+        object: (the text as bytes, rec_end as uint64 array, summary dict).  TGSF_TEXT_CAPACITY raises TgsfError(-4); its
+        `summary` attribute says what is needed."""
+        reads = np.ascontiguousarray(reads, dtype=abi.READ_RESULT_DTYPE)
+        frags = np.ascontiguousarray(frags, dtype=abi.FRAGMENT_DTYPE)
+        out, cap = self._out(out, out_capacity)
+        rec_end = np.zeros(max(len(frags), 1), np.uint64)
+        s = OutSummary()
+        rc = self.lib.tgsf_text_format(self.h, int(n_records), int(fasta), reads.ctypes.data, frags.ctypes.data, len(frags), int(fastq_out),
+                                       out.ctypes.data, cap, rec_end.ctypes.data, C.byref(s))
+        self._chk_out(rc, s)
+        return out[:s.n_bytes].tobytes(), rec_end[:s.n_records].copy(), s.as_dict()
+
+    def _chk_out(self, rc, s):
+        if rc != 0:
+            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            e.summary = s.as_dict()
+            raise e
+
+    def format_device(self, n_records, d_reads, d_frags, n_frags, fastq_out=True, fasta=False, d_text=None, d_index: IndexArrays | None = None,
+                      d_out=None, out_capacity=0, d_rec_end=None, d_summary=None, stream=None):
+        """Enqueue the format of tables already in HBM (device addresses) without waiting; None: the object's own text,
+        index, output buffer and summary."""
+        self._chk(self.lib.tgsf_text_format_device(self.h, d_text, C.byref(d_index) if d_index is not None else None, int(n_records),
+                                                   int(fasta), d_reads, d_frags, int(n_frags), int(fastq_out), d_out, int(out_capacity),
+                                                   d_rec_end, d_summary, stream))
+
+    def stage_ms(self):
+        """Milliseconds of the last format's stages (sizes, layout, copy) with profile() on; waits for it."""
+        ms = (C.c_float * 3)()
+        self._chk(self.lib.tgsf_text_out_stage_ms(self.h, C.byref(ms)))
+        return {"sizes": ms[0], "layout": ms[1], "copy": ms[2]}
+
+    def filter(self, ctx, text, fasta=False, final=True, fastq_out=None, out=None, out_capacity=None, frag_capacity=None, want_results=False):
+        """Text in, clean text out: (the text as bytes, rec_end, out summary dict, in summary dict) for the regular prefix
+        of `text`; with want_results also the per-read records and the fragments, as submit() returns them."""
+        t = _as_u8(text)
+        if fastq_out is None:
+            fastq_out = not fasta
+        out, cap = self._out(out, out_capacity)
+        rec_end = np.zeros(max(getattr(self, "max_frags", 0), 1), np.uint64)
+        so, si = OutSummary(), Summary()
+        bo = reads = frags = None
+        if want_results:
+            if frag_capacity is None:
+                frag_capacity = t.size // 100 + self.max_records + 16
+            reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
+            frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
+            bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
+        rc = self.lib.tgsf_text_filter(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final), int(fastq_out), out.ctypes.data, cap,
+                                       rec_end.ctypes.data, C.byref(so), C.byref(si), None, C.byref(bo) if bo is not None else None)
+        self._chk_out(rc, so)
+        res = (out[:so.n_bytes].tobytes(), rec_end[:so.n_records].copy(), so.as_dict(), si.as_dict())
+        if want_results:
+            res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
+        return res
