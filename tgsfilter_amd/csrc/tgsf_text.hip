@@ -4,46 +4,21 @@
 // Built two ways from this one source, like tgsf_lib.hip:
 //   hipcc --offload-arch=gfx950  -ltgsf       -> tgsfilter_amd/libtgsf_text.so      (the product)
 //   g++ -x c++ -DTGSF_EMUL       -ltgsf_emul  -> tests/emul/libtgsf_text_emul.so    (serial emulation; test infrastructure)
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
 #include <algorithm>
-#include <string>
-#include <vector>
 
+#include "tgsf_text_kernels.h"
+constexpr size_t kErrorCap = 768;          // bytes of an error text (fail)
+#include "tgsf_rt.h"                       // the runtime layer: HIP, or the serial emulation's (test infrastructure)
 #if defined(TGSF_EMUL)
-#include "tgsf_text_kernels.h"
 namespace tgsf_emul { thread_local Dim3 threadIdx, blockIdx, blockDim, gridDim; }
-typedef void* rt_stream;
-#include "tgsf_emul_rt.h"
-#else
-#include <hip/hip_runtime.h>
-#include "tgsf_text_kernels.h"
-typedef hipStream_t rt_stream;
-static int rt_malloc(void** p, size_t n) { return (int)hipMalloc(p, n ? n : 1); }
-static void rt_free(void* p) { (void)hipFree(p); }
-static int rt_memset(void* p, int v, size_t n, rt_stream s) { return (int)hipMemsetAsync(p, v, n, s); }
-static int rt_h2d(void* d, const void* s, size_t n, rt_stream st) { return (int)hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, st); }
-static int rt_d2h(void* d, const void* s, size_t n, rt_stream st) { return (int)hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, st); }
-static int rt_sync(rt_stream s) { return (int)hipStreamSynchronize(s); }
-static const char* rt_errstr(int e) { return hipGetErrorString((hipError_t)e); }
-#define TGSF_LAUNCH(kernel, grid, block, stream, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (stream), __VA_ARGS__)
-#define TGSF_LAUNCH_COOP TGSF_LAUNCH
-static unsigned grid_cap(unsigned g) { return g; }
 #endif
 
 using namespace tgsf;
 
-static thread_local std::string g_create_error;
-
-struct tgsf_text {
-    int device;
+struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exact, the text has TGSF_TEXT_PAD)
     uint64_t max_bytes, max_pieces;
     uint32_t max_records;
     rt_stream stream;
-    std::string error;
     bool profile = false;
     // device memory
     uint8_t* d_text = nullptr;          // max_bytes rounded up to 16, + TGSF_TEXT_PAD
@@ -74,35 +49,12 @@ struct tgsf_text {
     uint64_t* d_orec_end = nullptr;
     uint8_t* d_out = nullptr;
     tgsf_text_out_summary* d_osummary = nullptr;
-    std::vector<void*> allocs;
-#if !defined(TGSF_EMUL)
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    // around the last index, and around the stages of the last format (profile)
+    rt_event ev[2] = {nullptr, nullptr};
     bool ev_recorded = false;
-    hipEvent_t oev[4] = {nullptr, nullptr, nullptr, nullptr};
+    rt_event oev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool oev_recorded = false;
-#endif
 };
-
-static int fail(tgsf_text* tx, int code, const char* fmt, ...)
-{
-    char buf[768];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (tx) tx->error = buf; else g_create_error = buf;
-    return code;
-}
-
-template <class T>
-static int dev_alloc(tgsf_text* tx, T** p, size_t count)
-{
-    void* q = nullptr;
-    if (rt_malloc(&q, count * sizeof(T))) return 1;
-    tx->allocs.push_back(q);
-    *p = (T*)q;
-    return 0;
-}
 
 extern "C" int tgsf_text_abi_version(void) { return TGSF_TEXT_ABI_VERSION; }
 extern "C" const char* tgsf_text_backend(void) { return kTgsfEmul ? "emulation" : "hip:gfx950"; }
@@ -111,13 +63,11 @@ extern "C" const char* tgsf_text_last_error(tgsf_text* tx) { return tx ? tx->err
 extern "C" void tgsf_text_destroy(tgsf_text* tx)
 {
     if (!tx) return;
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-    if (tx->stream) { (void)hipStreamSynchronize(tx->stream); (void)hipStreamDestroy(tx->stream); }
-    for (hipEvent_t e : tx->ev) if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : tx->oev) if (e) (void)hipEventDestroy(e);
-#endif
-    for (void* p : tx->allocs) rt_free(p);
+    (void)rt_set_device(tx->device);
+    if (tx->stream) { (void)rt_sync(tx->stream); rt_stream_destroy(tx->stream); }
+    for (rt_event e : tx->ev) rt_event_destroy(e);
+    for (rt_event e : tx->oev) rt_event_destroy(e);
+    dev_free_all(tx);
     delete tx;
 }
 
@@ -136,11 +86,9 @@ extern "C" int tgsf_text_create(int device, uint64_t max_bytes, uint32_t max_rec
     tx->max_records = max_records;
     tx->max_pieces = (max_bytes + kTextPiece - 1) / kTextPiece;
     tx->stream = nullptr;
-#if !defined(TGSF_EMUL)
-    if (hipSetDevice(device) != hipSuccess) { delete tx; return fail(nullptr, TGSF_E_NO_DEVICE, "hipSetDevice(%d) failed: no usable HIP device (there is no CPU fallback)", device); }
-    if (hipStreamCreateWithFlags(&tx->stream, hipStreamNonBlocking) != hipSuccess) { delete tx; return fail(nullptr, TGSF_E_HIP, "stream creation failed"); }
-    for (hipEvent_t& e : tx->ev) if (hipEventCreate(&e) != hipSuccess) { tgsf_text_destroy(tx); return fail(nullptr, TGSF_E_HIP, "event creation failed"); }
-#endif
+    if (rt_set_device(device)) { delete tx; return fail(nullptr, TGSF_E_NO_DEVICE, "hipSetDevice(%d) failed: no usable HIP device (there is no CPU fallback)", device); }
+    if (rt_stream_create(&tx->stream)) { delete tx; return fail(nullptr, TGSF_E_HIP, "stream creation failed"); }
+    for (rt_event& e : tx->ev) if (rt_event_create(&e)) { tgsf_text_destroy(tx); return fail(nullptr, TGSF_E_HIP, "event creation failed"); }
     const uint64_t text_bytes = ((max_bytes + 15u) & ~15ull) + TGSF_TEXT_PAD;
     int e = 0;
     e |= dev_alloc(tx, &tx->d_text, text_bytes);
@@ -198,9 +146,7 @@ static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int f
     const unsigned gemit = blocks_for((pieces + kTextEmitPieces - 1) / kTextEmitPieces * kTextLanes, kTextThreads);
     const unsigned gsmall = grid_cap(std::min(blocks_for(tx->max_records, kTextThreads), 2048u));
     const unsigned gfold = std::min(gsmall, 64u);                                  // every wave ends in two atomics on one word each
-#if !defined(TGSF_EMUL)
-    if (tx->profile) { (void)hipEventRecord(tx->ev[0], st); }
-#endif
+    if (tx->profile) (void)rt_event_record(tx->ev[0], st);
     if (pieces) {
         TGSF_LAUNCH(k_text_mark, gwave, kTextThreads, st, d_text, n, pieces, (uint16_t*)tx->d_bits, tx->d_cnt);
         TGSF_LAUNCH_COOP(k_text_scan_tiles, nb, 256, st, tx->d_cnt, pieces, tx->d_part);
@@ -212,22 +158,17 @@ static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int f
     TGSF_LAUNCH(k_text_check, gsmall, kTextThreads, st, d_text, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, tx->d_state, I);
     TGSF_LAUNCH(k_text_fold, gfold, kTextThreads, st, (const uint32_t*)I.len, fasta, tx->max_records, tx->d_state);
     TGSF_LAUNCH_COOP(k_text_finish, 1, 64, st, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, (const TextState*)tx->d_state, d_summary);
-#if !defined(TGSF_EMUL)
-    if (tx->profile) { (void)hipEventRecord(tx->ev[1], st); tx->ev_recorded = true; }
-    if (hipGetLastError() != hipSuccess) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-#endif
+    if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
     return TGSF_OK;
 }
 
 // milliseconds between the events around the last index; the stream has been synchronised
 static float index_ms(tgsf_text* tx)
 {
-#if !defined(TGSF_EMUL)
     float ms = 0.0f;
-    if (tx->profile && tx->ev_recorded && hipEventElapsedTime(&ms, tx->ev[0], tx->ev[1]) == hipSuccess) { tx->ev_recorded = false; return ms; }
-    (void)hipGetLastError();
-#endif
-    (void)tx;
+    if (tx->profile && tx->ev_recorded && !rt_event_ms(&ms, tx->ev[0], tx->ev[1])) { tx->ev_recorded = false; return ms; }
+    (void)rt_last_error();
     return 0.0f;
 }
 
@@ -236,6 +177,14 @@ static int check_args(tgsf_text* tx, uint64_t n_bytes, int fasta, int final)
     if ((fasta != 0 && fasta != 1) || (final != 0 && final != 1)) return fail(tx, TGSF_E_INVALID, "fasta and final are 0 or 1");
     if (n_bytes > tx->max_bytes)
         return fail(tx, TGSF_E_CAPACITY, "text of %llu bytes, the indexer was created for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_bytes);
+    return TGSF_OK;
+}
+
+// a caller's index arrays on the device (NULL: the object's own)
+static int check_index(tgsf_text* tx, const tgsf_text_index_arrays* d_index)
+{
+    if (d_index && (!d_index->seq_off || !d_index->qual_off || !d_index->len || !d_index->name_off || !d_index->name_len))
+        return fail(tx, TGSF_E_INVALID, "a device index needs all five arrays");
     return TGSF_OK;
 }
 
@@ -251,13 +200,10 @@ extern "C" int tgsf_text_upload(tgsf_text* tx, const uint8_t* text, uint64_t n_b
 {
     if (!tx) return TGSF_E_INVALID;
     if (!text && n_bytes) return fail(tx, TGSF_E_INVALID, "null text");
-    if (n_bytes > tx->max_bytes)
-        return fail(tx, TGSF_E_CAPACITY, "text of %llu bytes, the indexer was created for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_bytes);
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
-    int e = upload(tx, text, n_bytes);
+    int e = check_args(tx, n_bytes, 0, 0);
     if (e) return e;
+    (void)rt_set_device(tx->device);
+    if ((e = upload(tx, text, n_bytes))) return e;
     const int he = rt_sync(tx->stream);
     return he ? fail(tx, TGSF_E_HIP, "stream synchronize failed: %s", rt_errstr(he)) : TGSF_OK;
 }
@@ -270,11 +216,8 @@ extern "C" int tgsf_text_index_device(tgsf_text* tx, const uint8_t* d_text, uint
     if (e) return e;
     if (!d_text) d_text = tx->d_text;
     if ((uintptr_t)d_text & 15u) return fail(tx, TGSF_E_INVALID, "the device text must be 16-byte aligned");
-    if (d_index && (!d_index->seq_off || !d_index->qual_off || !d_index->len || !d_index->name_off || !d_index->name_len))
-        return fail(tx, TGSF_E_INVALID, "a device index needs all five arrays");
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    if ((e = check_index(tx, d_index))) return e;
+    (void)rt_set_device(tx->device);
     return enqueue_index(tx, d_text, n_bytes, fasta, final, d_index ? *d_index : tx->d_index, d_summary ? d_summary : tx->d_summary,
                          hip_stream ? (rt_stream)hip_stream : tx->stream);
 }
@@ -303,9 +246,7 @@ static int fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_te
 extern "C" int tgsf_text_fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary)
 {
     if (!tx) return TGSF_E_INVALID;
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    (void)rt_set_device(tx->device);
     tgsf_text_summary sum;
     return fetch(tx, out_index, out_summary, &sum);
 }
@@ -317,9 +258,7 @@ extern "C" int tgsf_text_index(tgsf_text* tx, const uint8_t* text, uint64_t n_by
     if (!out_summary || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
     int e = check_args(tx, n_bytes, fasta, final);
     if (e) return e;
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    (void)rt_set_device(tx->device);
     if ((e = upload(tx, text, n_bytes))) return e;
     if ((e = enqueue_index(tx, tx->d_text, n_bytes, fasta, final, tx->d_index, tx->d_summary, tx->stream))) return e;
     tgsf_text_summary sum;
@@ -397,9 +336,7 @@ extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* tex
     if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
     int e = check_args(tx, n_bytes, fasta, final);
     if (e) return e;
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    (void)rt_set_device(tx->device);
     if ((e = grow_frags(tx, bo))) return e;
     uint32_t nf = 0;
     return submit_core(tx, ctx, text, n_bytes, fasta, final, out_index, out_summary, bo, bo->frags ? tx->d_frags : nullptr,
@@ -412,10 +349,8 @@ extern "C" int tgsf_text_out_reserve(tgsf_text* tx, uint32_t max_frags, uint64_t
     if (!tx) return TGSF_E_INVALID;
     if (tx->out_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_out_reserve has been called already (%u fragments, %llu bytes)", tx->max_frags, (unsigned long long)tx->max_out);
     if (max_frags == 0 || max_out_bytes == 0) return fail(tx, TGSF_E_INVALID, "max_frags and max_out_bytes must be positive");
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-    for (hipEvent_t& ev : tx->oev) if (!ev && hipEventCreate(&ev) != hipSuccess) return fail(tx, TGSF_E_HIP, "event creation failed");
-#endif
+    (void)rt_set_device(tx->device);
+    for (rt_event& ev : tx->oev) if (!ev && rt_event_create(&ev)) return fail(tx, TGSF_E_HIP, "event creation failed");
     const size_t parts = (size_t)max_frags / kTextScanTile + 2;
     int e = 0;
     e |= dev_alloc(tx, &tx->d_out, ((max_out_bytes + 15u) & ~15ull));
@@ -457,37 +392,25 @@ static int enqueue_format(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_
     // a wave per 4 KiB piece of the output, as many as the capacity has, at most a few per SIMD of the device: they stride
     const unsigned gcopy = grid_cap(std::min(std::max(blocks_for(((capacity + kTextPiece - 1) / kTextPiece) * kTextLanes, kTextThreads), 1u), 2048u));
     TextOutState* S = tx->d_ostate;
-#if !defined(TGSF_EMUL)
-    if (tx->profile) { (void)hipEventRecord(tx->oev[0], st); }
-#endif
+    if (tx->profile) (void)rt_event_record(tx->oev[0], st);
     TGSF_LAUNCH(k_textout_flag, gfrag, kTextThreads, st, d_frags, n, tx->d_opass, S);
     if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles, nb, 256, st, tx->d_opass, n, tx->d_opass_part);
     TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_opass_part, nb, &S->n_records);
-    if (n) {
+    if (n)
         TGSF_LAUNCH(k_textout_size, gfrag, kTextThreads, st, d_text, I, d_reads, d_frags, n, fastq_out, (const uint32_t*)tx->d_opass,
                     (const uint64_t*)tx->d_opass_part, tx->d_osize, tx->d_ometa, S);
-#if !defined(TGSF_EMUL)
-        if (tx->profile) { (void)hipEventRecord(tx->oev[1], st); }
-#endif
-        TGSF_LAUNCH_COOP(k_textout_scan_tiles64, nb, 256, st, tx->d_osize, n, tx->d_osize_part);
-    }
-#if !defined(TGSF_EMUL)
-    else if (tx->profile) { (void)hipEventRecord(tx->oev[1], st); }
-#endif
+    if (tx->profile) (void)rt_event_record(tx->oev[1], st);
+    if (n) TGSF_LAUNCH_COOP(k_textout_scan_tiles64, nb, 256, st, tx->d_osize, n, tx->d_osize_part);
     TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_osize_part, nb, &S->n_bytes);
     TGSF_LAUNCH(k_textout_finish, gfrag, kTextThreads, st, (const uint64_t*)tx->d_osize, (const uint64_t*)tx->d_osize_part,
                 (const uint32_t*)tx->d_opass, (const uint64_t*)tx->d_opass_part, (const TextOutMeta*)tx->d_ometa, n, capacity,
                 (const TextOutState*)S, tx->d_oends, d_rec_end, d_summary);
-#if !defined(TGSF_EMUL)
-    if (tx->profile) { (void)hipEventRecord(tx->oev[2], st); }
-#endif
+    if (tx->profile) (void)rt_event_record(tx->oev[2], st);
     if (n)
         TGSF_LAUNCH(k_textout_copy, gcopy, kTextThreads, st, d_text, I, d_frags, (const TextOutMeta*)tx->d_ometa, (const uint64_t*)tx->d_oends,
                     n, fastq_out, (const TextOutState*)S, capacity, d_out);
-#if !defined(TGSF_EMUL)
-    if (tx->profile) { (void)hipEventRecord(tx->oev[3], st); tx->oev_recorded = true; }
-    if (hipGetLastError() != hipSuccess) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-#endif
+    if (tx->profile) { (void)rt_event_record(tx->oev[3], st); tx->oev_recorded = true; }
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
     return TGSF_OK;
 }
 
@@ -496,17 +419,14 @@ static float format_ms(tgsf_text* tx, float* ms)
 {
     float sum = 0.0f;
     if (ms) ms[0] = ms[1] = ms[2] = 0.0f;
-#if !defined(TGSF_EMUL)
     if (tx->profile && tx->oev_recorded) {
         for (int k = 0; k < 3; k++) {
             float t = 0.0f;
-            if (hipEventElapsedTime(&t, tx->oev[k], tx->oev[k + 1]) != hipSuccess) { (void)hipGetLastError(); return 0.0f; }
+            if (rt_event_ms(&t, tx->oev[k], tx->oev[k + 1])) { (void)rt_last_error(); return 0.0f; }
             if (ms) ms[k] = t;
             sum += t;
         }
     }
-#endif
-    (void)tx;
     return sum;
 }
 
@@ -514,10 +434,8 @@ extern "C" int tgsf_text_out_stage_ms(tgsf_text* tx, float ms[3])
 {
     if (!tx) return TGSF_E_INVALID;
     if (!ms) return fail(tx, TGSF_E_INVALID, "null argument");
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-    if (tx->profile && tx->oev_recorded && hipEventSynchronize(tx->oev[3]) != hipSuccess) return fail(tx, TGSF_E_HIP, "waiting for the format failed");
-#endif
+    (void)rt_set_device(tx->device);
+    if (tx->profile && tx->oev_recorded && rt_event_sync(tx->oev[3])) return fail(tx, TGSF_E_HIP, "waiting for the format failed");
     (void)format_ms(tx, ms);
     return TGSF_OK;
 }
@@ -531,15 +449,12 @@ extern "C" int tgsf_text_format_device(tgsf_text* tx, const uint8_t* d_text, con
     int e = check_format(tx, n_frags, fasta, fastq_out);
     if (e) return e;
     if (n_frags && (!d_reads || !d_frags || !n_records)) return fail(tx, TGSF_E_INVALID, "fragments without their table or without the per-read records");
-    if (d_index && (!d_index->seq_off || !d_index->qual_off || !d_index->len || !d_index->name_off || !d_index->name_len))
-        return fail(tx, TGSF_E_INVALID, "a device index needs all five arrays");
+    if ((e = check_index(tx, d_index))) return e;
     if (!d_index && n_records > tx->max_records)
         return fail(tx, TGSF_E_CAPACITY, "%u records, the object's index arrays hold %u", n_records, tx->max_records);
     if ((uintptr_t)d_out & 15u) return fail(tx, TGSF_E_INVALID, "the device output buffer must be 16-byte aligned");
     if (!d_out) { d_out = tx->d_out; out_capacity = std::min(out_capacity, tx->max_out); }
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    (void)rt_set_device(tx->device);
     return enqueue_format(tx, d_text ? d_text : tx->d_text, d_index ? *d_index : tx->d_index, d_reads, d_frags, n_frags, fastq_out, d_out,
                           out_capacity, d_rec_end, d_summary ? d_summary : tx->d_osummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
 }
@@ -577,9 +492,7 @@ extern "C" int tgsf_text_format(tgsf_text* tx, uint32_t n_records, int fasta, co
     if (e) return e;
     if (!out_summary || (!out && out_capacity) || (n_frags && (!reads || !frags || !n_records))) return fail(tx, TGSF_E_INVALID, "null argument: summary, output buffer or tables");
     if (n_records > tx->max_records) return fail(tx, TGSF_E_CAPACITY, "%u records, the object's index arrays hold %u", n_records, tx->max_records);
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    (void)rt_set_device(tx->device);
     int he = 0;
     if (n_frags) {
         he |= rt_h2d(tx->d_reads, reads, (size_t)n_records * sizeof(tgsf_read_result), tx->stream);
@@ -599,9 +512,7 @@ extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* tex
     int e = check_format(tx, 0, fasta, fastq_out);
     if (!e) e = check_args(tx, n_bytes, fasta, final);
     if (e) return e;
-#if !defined(TGSF_EMUL)
-    (void)hipSetDevice(tx->device);
-#endif
+    (void)rt_set_device(tx->device);
     const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts, as in tgsf_text_submit
     if (down && (e = grow_frags(tx, bo))) return e;
     tgsf_fragment* d_fr = down ? tx->d_frags : tx->d_ofrags;

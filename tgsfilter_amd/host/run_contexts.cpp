@@ -101,7 +101,7 @@ void Run::make_contexts()
     // match lengths ~350 KB: keep it under 4 GB per context
     batch_reads = 1u << 16;
     {
-        // (the library's rule, tgsf_lib.hip: every alignment of a batch gets the columns of the longest one, and the
+        // (the library's rule, tgsf_lib.hip, size_context: every alignment of a batch gets the columns of the longest one, and the
         // words of the widest column class any adapter needs -- 1 / 2 / 4 words up to 64 / 128 / 256 bp, 20 beyond)
         uint64_t per_read = 0, cols = 0, words = 1;
         for (const std::string& a : adapters) {
