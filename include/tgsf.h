@@ -64,7 +64,7 @@ typedef enum tgsf_status {
  */
 typedef struct tgsf_params {
     uint32_t struct_size;     /* = sizeof(tgsf_params); ABI guard                    */
-    int32_t  min_len;         /* -l  MinLen                                           */
+    int32_t  min_len;         /* -l  MinLen, >= 0 (below: TGSF_E_INVALID); the reference itself clamps -l to 100 (:232-234) */
     int32_t  max_len;         /* -L  MaxLen                                           */
     float    min_q;           /* -q  MinQ (resolved, >= 0)                            */
     float    max_q;           /* -Q  MaxQ                                             */

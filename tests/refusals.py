@@ -330,6 +330,40 @@ def text_over_capacity(lib_path, text_lib_path):
         ctx_big.close()
 
 
+def min_len_below_zero(lib_path, text_lib_path):
+    """tgsf_params.min_len < 0: tgsf_create refuses it in front of the device (with a negative min_len k_prepare would
+    speculate on reads shorter than their trims), so no context exists for tgsf_text_filter to take either -- it answers a
+    NULL context with TGSF_E_INVALID and runs nothing.  min_len = 0 is the domain's edge: the one-call form then gives the
+    oracle's records and fragments, reads shorter than the trims among them."""
+    from tests import textoutparity as top
+    from tests import textparity
+    from tgsfilter_amd import text as tgtext
+    rng = np.random.default_rng(29)
+    reads = synth.make_reads(29, 24, "ont", mean_len=1500, max_len=5000, zoo=True, pmid=0.1)
+    for L in (3, 2000, 4, 1500, 7, 12, 13, HEAD + TAIL, HEAD + TAIL + 1):
+        reads.insert(int(rng.integers(0, len(reads))), (b"short%d" % L, np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, L)].tobytes(),
+                                                        (rng.integers(25, 40, L) + 33).astype(np.uint8).tobytes()))
+    text = textparity.fastq_of(reads)
+    p = seam_params(reads)
+    for bad in (-1, -(1 << 31)):
+        p.min_len = bad
+        raises(lambda: capi.Context(p, 0, lib_path), abi.E_INVALID, "min_len")
+
+    class NoContext:
+        h = None
+    fr = top.frag_room(len(text), len(reads))
+    tx = tgtext.TextIndexer(0, len(text), len(reads), text_lib_path)
+    try:
+        tx.reserve_output(fr, top.out_room(len(text), fr))
+        raises(lambda: tx.filter(NoContext(), text), abi.E_INVALID, "null argument")
+    finally:
+        tx.close()
+    p.min_len = 0
+    ix, er, ef = top.oracle_on_text(p, text)
+    assert (ef["len"][(ef["flags"] & abi.FF_PASS) != 0] < 100).any()
+    top.one_call(lib_path, text_lib_path, p, text, len(reads), False, True, top.expected(text, ix, er, ef, True), (er, ef), "min_len 0")
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. refusals decided on the device
 # ---------------------------------------------------------------------------------------------------------------------

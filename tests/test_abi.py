@@ -90,6 +90,7 @@ CREATE_REFUSALS = [
     (dict(struct_size=0), abi.E_INVALID, "struct_size"),
     (dict(n_adapters=-1), abi.E_INVALID, "n_adapters"),
     (dict(n_adapters=33), abi.E_INVALID, "n_adapters"),
+    (dict(min_len=-1), abi.E_INVALID, "min_len"),
     (dict(kmer=0), abi.E_UNSUPPORTED, "kmer (-k) 0"),
     (dict(kmer=33), abi.E_UNSUPPORTED, "kmer (-k) 33"),
     (dict(qtype=32), abi.E_INVALID, "qtype"),
@@ -111,7 +112,7 @@ CREATE_REFUSALS = [
     (dict(max_read_len=(1 << 28) + 1), abi.E_INVALID, "max_read_len"),
 ]
 # the accepting neighbours that are cheap (small contexts; no context with max_read_len near 2^28 is created)
-CREATE_ACCEPTED = [dict(kmer=1), dict(kmer=32), dict(kmer=0, min_repeat=0), dict(kmer=33, min_repeat=0), dict(qtype=33), dict(qtype=64),
+CREATE_ACCEPTED = [dict(min_len=0), dict(kmer=1), dict(kmer=32), dict(kmer=0, min_repeat=0), dict(kmer=33, min_repeat=0), dict(qtype=33), dict(qtype=64),
                    dict(bc_len=0), dict(end_len=0, extra_len=0), dict(end_match_len=1, mid_match_len=1)]
 
 

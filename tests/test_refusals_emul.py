@@ -30,6 +30,11 @@ def test_emul_text_larger_than_the_context_takes(emul):
     refusals.text_over_capacity(emul, os.path.join(EMUL_DIR, "libtgsf_text_emul.so"))
 
 
+def test_emul_min_len_below_zero_is_refused_for_the_text_filter_too(emul):
+    subprocess.run(["make", "-s", "-C", EMUL_DIR, "-f", "Makefile.text"], check=True)
+    refusals.min_len_below_zero(emul, os.path.join(EMUL_DIR, "libtgsf_text_emul.so"))
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("at", [0, 7, 256, -1])
 @pytest.mark.parametrize("kind", ["len0", "offsets", "over"])

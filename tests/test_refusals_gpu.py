@@ -18,6 +18,10 @@ def test_gpu_text_larger_than_the_context_takes():
     refusals.text_over_capacity(None, None)
 
 
+def test_gpu_min_len_below_zero_is_refused_for_the_text_filter_too():
+    refusals.min_len_below_zero(None, None)
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("at", [0, 7, 256, -1])
 @pytest.mark.parametrize("kind", ["len0", "offsets", "over"])

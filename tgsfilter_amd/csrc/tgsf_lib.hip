@@ -325,6 +325,8 @@ static int check_params(const tgsf_params* p)
         return fail(nullptr, TGSF_E_INVALID, "n_adapters %d outside [0,%d]", p->n_adapters, TGSF_MAX_ADAPTERS);
     if (p->min_repeat > 0 && (p->kmer < 1 || p->kmer > 32))
         return fail(nullptr, TGSF_E_UNSUPPORTED, "kmer (-k) %d: the repeat gate supports k-mer sizes 1..32 (the reference's k-mers are 64 bits)", p->kmer);
+    // (a negative min_len lets a read shorter than its trims pass for a kept one in k_prepare's speculation: L - tail_trim is then formed in 32 unsigned bits)
+    if (p->min_len < 0) return fail(nullptr, TGSF_E_INVALID, "min_len (-l) %d: must be >= 0", p->min_len);
     if (p->qtype != 33 && p->qtype != 64) return fail(nullptr, TGSF_E_INVALID, "qtype must be 33 or 64");
     if (p->bc_len < 0 || p->bc_len > kMaxBcLenTotal) return fail(nullptr, TGSF_E_INVALID, "bc_len (-e) outside [0,%d]", kMaxBcLenTotal);
     if (p->filter && p->n_adapters > 0) {
