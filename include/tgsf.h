@@ -71,11 +71,11 @@ typedef struct tgsf_params {
     int32_t  bc_len;          /* -e  BCLen: positions in the 5'/3' QC tables          */
     int32_t  head_trim;       /* -5  HeadTrim (resolved; <= 0 disables, :1334)        */
     int32_t  tail_trim;       /* -3  TailTrim                                         */
-    int32_t  end_len;         /* -E  EndLen                                           */
+    int32_t  end_len;         /* -E  EndLen, 0 .. 2^28 (above: TGSF_E_INVALID); beyond a read's length the value changes nothing: windows are clamped to the read */
     int32_t  end_match_len;   /* -m  EndMatchLen                                      */
     int32_t  mid_match_len;   /* -M  MidMatchLen                                      */
-    int32_t  extra_len;       /* -T  ExtraLen                                         */
-    float    end_sim;         /* -s  EndSim                                           */
+    int32_t  extra_len;       /* -T  ExtraLen, 0 .. 2^28 (above: TGSF_E_INVALID)      */
+    float    end_sim;         /* -s  EndSim: any positive value is taken (+inf: no end adapter passes; tiny: the end window is the whole read) */
     float    mid_sim;         /* -S  MidSim                                           */
     int32_t  discard;         /* -D  discard reads with a middle adapter              */
     int32_t  filter;          /* Para_A24::Filter (0 with -F / --qc)                  */

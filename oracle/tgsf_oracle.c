@@ -391,7 +391,10 @@ static void get_edit_distance(const tgsf_params* p, const uint8_t* q, int Q,
         }
     }
     /* ends: :1266-1321 */
-    int check = E + (int)((float)Q / p->end_sim);                  /* :1267 int(qLen / endSim), float division */
+    /* :1267 int(qLen / endSim), float division; a quotient the conversion cannot take (undefined) stands for 2^28: the
+       window is clamped to the read below, and include/tgsf.h bounds a read's length and end_len by 2^28 */
+    float quot = (float)Q / p->end_sim;
+    int check = E + (quot < 268435456.0f ? (int)quot : 268435456);
     if (check > L) check = L;
     max_k = Q - p->end_match_len + 1;
     if (check >= 5) {

@@ -81,18 +81,44 @@ def random_case(seed: int, n_reads: int):
         # (the context sized as the product sizes it, tests/sizing.py, instead of cut to fit the batch -- again a stream of its own)
         r3 = np.random.default_rng(seed ^ 0x0512E5ED)
         kw["_sizing"] = str(r3.choice(["exact", "indexed", "streamed", str(r3.choice(list(sizing.SEAMS)))]))
+    if os.environ.get("TGSF_FUZZ_SEARCH") == "1":
+        # (the adapter search over its parameters and adapter sets, tests/search_domain.py -- once more a stream of its own: 1..32
+        # adapters from the pools and random ones of 5..300 bp, a copy of one of them in most reads, -E and -T from 0 to 10^6, match
+        # lengths from 1 to one above an adapter's length, similarities that sit exactly on a float32 m / Q)
+        r4 = np.random.default_rng(seed ^ 0x5EA2C4AD)
+        both = LIB_ADAPTERS + WIDE_ADAPTERS
+        na = int(r4.integers(1, 33))
+        ads = [both[i] for i in r4.choice(len(both), min(na, int(r4.integers(0, len(both) + 1))), replace=False)]
+        acgt = np.frombuffer(b"ACGT", dtype=np.uint8)
+        ads += [bytes(acgt[r4.integers(0, 4, int(r4.integers(5, 301)))]) for _ in range(na - len(ads))]
+        ads = [ads[i] for i in r4.permutation(na)]
+        long_enough = [a for a in ads if len(a) >= 20] or ads
+        reads = synth.make_reads(int(r4.integers(1, 1 << 30)), n_reads, kind, mean_len=float(r4.choice([300, 800, 2500])), zoo=bool(r4.random() < 0.7),
+                                 pmid=float(r4.choice([0.0, 0.3, 0.6])), adapter=long_enough[int(r4.integers(0, len(long_enough)))])
+        Q = len(ads[int(r4.integers(0, na))])
+
+        def sim():
+            m = int(r4.integers(max(1, Q // 2), Q + 1))
+            return float(r4.choice([0.75, 0.9, 1.0, float(np.float32(m) / np.float32(Q)), float(np.nextafter(np.float32(m) / np.float32(Q), np.float32(2)))]))
+        kw.update(adapters=ads, filter=True, end_len=int(r4.choice([0, 1, 5, 27, 28, 60, 150, 1000, 10**6])), extra_len=int(r4.choice([0, 1, 50, 2000, 10**6])),
+                  end_match_len=int(r4.integers(1, Q + 2)), mid_match_len=int(r4.integers(1, Q + 2)), _end_sim=sim(), _mid_sim=sim(),
+                  _min_len=int(r4.choice([1, 50, 100])), _pool_cap=int(r4.choice([0, 0, 0, 3, 40])))
     return kind, reads, kw
 
 
 def run_case(lib_path, seed: int, n_reads: int):
     kind, reads, kw = random_case(seed, n_reads)
+    after = {k: kw.pop("_" + k) for k in ("end_sim", "mid_sim", "min_len") if "_" + k in kw}     # (fields make_params would clamp)
     pool_cap = kw.pop("_pool_cap", 0)
     force_bp = kw.pop("_force_by_product", False)
     hints = kw.pop("_sizing", "exact")
     outer_ct = os.environ.get("TGSF_CLEAN_TABLES")
     if force_bp:
         os.environ["TGSF_CLEAN_TABLES"] = "byproduct"
-    p = sizing.size(abi.make_params(kind, **kw), reads, hints)
+    p = abi.make_params(kind, **kw)
+    for k, v in after.items():
+        setattr(p, k, v)
+    p = sizing.size(p, reads, hints)
     outer = os.environ.get("TGSF_POOL_CAP")                 # (a campaign may set one for every case: keep it)
     if pool_cap:
         os.environ["TGSF_POOL_CAP"] = str(pool_cap)
@@ -109,9 +135,11 @@ def run_case(lib_path, seed: int, n_reads: int):
             else:
                 os.environ["TGSF_CLEAN_TABLES"] = outer_ct
     try:
+        # (a min_len below 100 -- the search stream's -- leaves more fragments than a hundredth of the bases)
+        room = sum(len(r[1]) for r in reads) // max(int(p.min_len), 1) + len(reads) + 16 if "min_len" in after else None
         parity.compare_batch(ctx, p, reads, align=int(np.random.default_rng(seed).choice([1, 16])),
-                             explicit_lengths=True)
+                             explicit_lengths=True, frag_capacity=room)
     except AssertionError as e:
-        raise AssertionError("fuzz seed %d (%s, %s, sized %s): %s" % (seed, kind, {k: v for k, v in kw.items() if k != "adapters"}, hints, e))
+        raise AssertionError("fuzz seed %d (%s, %s, sized %s): %s" % (seed, kind, dict({k: v for k, v in kw.items() if k != "adapters"}, **after), hints, e))
     finally:
         ctx.close()

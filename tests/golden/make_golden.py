@@ -128,6 +128,21 @@ CASES.update({
     "odd_bytes": (dict(seed=41, n=60, kind="ont", mean_len=2500, zoo=True, pmid=0.1), [synth.ONT_RAPID], "-x ont -l 500 -q 7 -5 7 -3 8 -e 200", "fq", "odd_bytes"),
 })
 
+SEARCH_17 = [synth.ONT_RAPID, synth.ONT_RAPID_RC, synth.PACBIO_BLUNT, synth.PACBIO_BLUNT_RC, b"AATGTACTTCGTTCAGTTACGTATTGCT", b"AGCAATACGTAACTGAACGAAGTACATT",
+             b"GCAATACGTAACTGAACGAAGT", b"ACTTCGTTCAGTTACGTATTGC", b"CTTGCGGGCGGCGGACTCTCCTCTGAAGATAGAGCGACAGGCAAG", LONG_ADAPTER, HUGE_A] + \
+            [bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.default_rng(1700 + L).integers(0, 4, L)]) for L in (20, 31, 33, 64, 65, 129)]
+CASES.update({
+    # the adapter search on the corners of its parameters (tests/search_domain.py): small inputs, 40 reads of about 1.5 kb.  -E 0 / 1 / 5
+    # and 100 000 (no read is long enough for the pre-pass to sample: qualities of 80 and above read as Phred+64 either way), -T 0 / 1 /
+    # 100 000, -m / -M one below, at and one above the adapter's 50 bp (one above: the adapter is never found), 17 adapters of 20..150 bp
+    "search_E0": (dict(seed=42, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), [synth.ONT_RAPID], "-x ont -l 100 -q 7 -5 0 -3 0 -E 0 -T 0 -m 49 -M 49"),
+    "search_E1": (dict(seed=43, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), [synth.ONT_RAPID], "-x ont -l 100 -q 7 -5 0 -3 0 -E 1 -T 1 -m 50 -M 50"),
+    "search_E5": (dict(seed=44, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), [synth.ONT_RAPID], "-x ont -l 100 -q 7 -5 0 -3 0 -E 5 -T 100000 -M 20"),
+    "search_m51": (dict(seed=45, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), [synth.ONT_RAPID], "-x ont -l 100 -q 7 -5 0 -3 0 -m 51 -M 51"),
+    "search_E100000": (dict(seed=46, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), [synth.ONT_RAPID], "-x ont -l 100 -5 0 -3 0 -E 100000 -T 1", "fq", "phred64"),
+    "search_a17": (dict(seed=47, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), SEARCH_17, "-x ont -l 100 -q 7 -5 0 -3 0 -M 20 -m 12"),
+})
+
 IN_EXT = {"fq": "in.fq", "bam": "in.bam", "sam": "in.sam", "fa": "in.fa"}
 
 

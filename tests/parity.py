@@ -20,16 +20,16 @@ def sized(p: abi.Params, reads, extra=1):
     return p
 
 
-def compare_batch(ctx: capi.Context, p: abi.Params, reads, *, align=16, explicit_lengths=True, base=None, expected=None):
+def compare_batch(ctx: capi.Context, p: abi.Params, reads, *, align=16, explicit_lengths=True, base=None, expected=None, frag_capacity=None):
     """Run one batch through the backend and the oracle; everything must be identical.  base: the tallies the context
     held before the batch (None: none) -- the oracle adds the batch to a copy of them.  expected: what orc.filter_batch
     returned for these reads, these parameters and that base (its results do not depend on the layout): the oracle is
-    not run again."""
+    not run again.  frag_capacity: room for fragments on both sides (None: a hundredth of the bases and one per read)."""
     seq, qual, offsets, lengths = synth.pack(reads, align=align)
     if explicit_lengths:
-        got_r, got_f = ctx.submit(seq, qual, offsets[:-1].copy() if align > 1 else offsets, lengths)
+        got_r, got_f = ctx.submit(seq, qual, offsets[:-1].copy() if align > 1 else offsets, lengths, frag_capacity=frag_capacity)
     else:
-        got_r, got_f = ctx.submit(seq, qual, offsets, None)
+        got_r, got_f = ctx.submit(seq, qual, offsets, None, frag_capacity=frag_capacity)
     ctr = ctx.counters()
     if expected is not None:
         exp_r, exp_f, exp_ctr = expected
@@ -37,7 +37,7 @@ def compare_batch(ctx: capi.Context, p: abi.Params, reads, *, align=16, explicit
     else:
         exp_ctr = np.zeros(ctx.ctr_words, dtype=np.uint64) if base is None else base.copy()
         exp_r, exp_f, exp_ctr = orc.filter_batch(p, seq, qual, offsets, lengths if explicit_lengths else None,
-                                                 n_bins=ctx.n_bins, ctr=exp_ctr)
+                                                 n_bins=ctx.n_bins, ctr=exp_ctr, frag_capacity=frag_capacity)
     for name in ("sum_q", "flags", "n_frags", "frag_begin", "trimmed"):
         bad = np.nonzero(got_r[name] != exp_r[name])[0]
         assert bad.size == 0, f"read field {name} differs at reads {bad[:8]}: got {got_r[name][bad[:8]]} exp {exp_r[name][bad[:8]]}"

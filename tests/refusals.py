@@ -364,6 +364,30 @@ def min_len_below_zero(lib_path, text_lib_path):
     top.one_call(lib_path, text_lib_path, p, text, len(reads), False, True, top.expected(text, ix, er, ef, True), (er, ef), "min_len 0")
 
 
+SEARCH_BOUND = 1 << 28          # the most end_len (-E) and extra_len (-T) may be: the cap on max_read_len
+
+
+def end_len_and_extra_len_above_their_bound(lib_path):
+    """tgsf_params.end_len / extra_len above 2^28: tgsf_create refuses them in front of the device, whether or not adapters are
+    searched for (k_gate_reads forms L - 2 * end_len, k_mid_resolve pos + end_len + 1 + extra_len in 32 signed bits: with
+    end_len = 1 500 000 000 a read got a middle window far outside itself).  tgsf_create only: no batch is submitted with
+    such a value.  The bound itself is taken, and a context that was created next to a refused one works."""
+    reads = synth.make_reads(28, 12, "ont", mean_len=1200, max_len=4000, zoo=True, pmid=0.2)
+    for field, flag in (("end_len", "-E"), ("extra_len", "-T")):
+        for bad in (SEARCH_BOUND + 1, 1_500_000_000, 2147483647):
+            for kw in ({}, {"filter": False}, {"adapters": []}):
+                p = seam_params(reads, **kw)
+                setattr(p, field, bad)
+                raises(lambda: capi.Context(p, 0, lib_path), abi.E_INVALID, "%s (%s) %d" % (field, flag, bad), "2^28")
+    p = seam_params(reads)
+    p.end_len = p.extra_len = SEARCH_BOUND
+    ctx = capi.Context(p, 0, lib_path)
+    try:
+        parity.compare_batch(ctx, p, reads)
+    finally:
+        ctx.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 2. refusals decided on the device
 # ---------------------------------------------------------------------------------------------------------------------

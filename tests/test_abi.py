@@ -91,6 +91,12 @@ CREATE_REFUSALS = [
     (dict(n_adapters=-1), abi.E_INVALID, "n_adapters"),
     (dict(n_adapters=33), abi.E_INVALID, "n_adapters"),
     (dict(min_len=-1), abi.E_INVALID, "min_len"),
+    (dict(end_len=(1 << 28) + 1), abi.E_INVALID, "end_len (-E)"),
+    (dict(end_len=2147483647), abi.E_INVALID, "end_len (-E)"),
+    (dict(extra_len=(1 << 28) + 1), abi.E_INVALID, "extra_len (-T)"),
+    (dict(extra_len=2147483647), abi.E_INVALID, "extra_len (-T)"),
+    (dict(end_len=1500000000, filter=0), abi.E_INVALID, "end_len (-E)"),        # (whether or not adapters are searched for)
+    (dict(extra_len=2147483647, n_adapters=0), abi.E_INVALID, "extra_len (-T)"),
     (dict(kmer=0), abi.E_UNSUPPORTED, "kmer (-k) 0"),
     (dict(kmer=33), abi.E_UNSUPPORTED, "kmer (-k) 33"),
     (dict(qtype=32), abi.E_INVALID, "qtype"),
@@ -113,7 +119,9 @@ CREATE_REFUSALS = [
 ]
 # the accepting neighbours that are cheap (small contexts; no context with max_read_len near 2^28 is created)
 CREATE_ACCEPTED = [dict(min_len=0), dict(kmer=1), dict(kmer=32), dict(kmer=0, min_repeat=0), dict(kmer=33, min_repeat=0), dict(qtype=33), dict(qtype=64),
-                   dict(bc_len=0), dict(end_len=0, extra_len=0), dict(end_match_len=1, mid_match_len=1)]
+                   dict(bc_len=0), dict(end_len=0, extra_len=0), dict(end_match_len=1, mid_match_len=1),
+                   dict(end_len=1 << 28, extra_len=1 << 28), dict(end_sim=1e-30), dict(end_sim=float("inf")),
+                   dict(end_match_len=2147483647, mid_match_len=2147483647)]
 
 
 @pytest.mark.parametrize("fields,code,names", CREATE_REFUSALS, ids=lambda v: "-".join("%s=%s" % kv for kv in v.items()) if isinstance(v, dict) else None)

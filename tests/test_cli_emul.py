@@ -206,3 +206,40 @@ def test_cli_usage_and_errors(binary, tmp_path):
     assert p.returncode == 1 and b"Error: Lack Argument for [ -l ]" in p.stderr
     p = subprocess.run([binary, "-i", str(f), "-o", "x.fq"], capture_output=True)
     assert b"Error: lack argument for the must: -x" in p.stderr
+
+
+@pytest.fixture(scope="module")
+def small_input(tmp_path_factory):
+    """40 ONT reads of about 2 kb with adapters at their ends and in the middle of some; quality bytes of 70..105, which read
+    as Phred+64 whether or not a read is long enough for the pre-pass to sample (none is, with -E of 100 000 and more)."""
+    import numpy as np
+    from tgsfilter_amd import synth
+    d = tmp_path_factory.mktemp("search_cli")
+    rng = np.random.default_rng(28)
+    reads = synth.make_reads(28, 40, "ont", mean_len=2000, zoo=True, pmid=0.3)
+    (d / "in.fq").write_bytes(b"".join(b"@%s\n%s\n+\n%s\n" % (n, s, rng.integers(70, 106, len(s), dtype=np.uint8).tobytes()) for n, s, _ in reads))
+    (d / "ad.fa").write_bytes(b">rapid\n%s\n>rapid_rc\n%s\n" % (synth.ONT_RAPID, synth.ONT_RAPID_RC))
+    return d
+
+
+@pytest.mark.parametrize("flag,value,field", [("-E", "1500000000", "end_len (-E)"), ("-T", "2147483647", "extra_len (-T)"), ("-E", "268435457", "end_len (-E)")])
+def test_cli_refuses_end_len_and_extra_len_above_their_bound(binary, small_input, tmp_path, flag, value, field):
+    """-E / -T above 2^28 (tgsf_create's bound, include/tgsf.h): a non-zero exit status, the library's message, no output file."""
+    out = tmp_path / "out.fq"
+    p = subprocess.run([binary, "-i", str(small_input / "in.fq"), "-a", str(small_input / "ad.fa"), "-o", str(out), "-x", "ont", "-5", "0", "-3", "0", flag, value],
+                       capture_output=True, timeout=120)
+    assert p.returncode not in (0, -11, 139) and p.returncode > 0, (p.returncode, p.stderr[-500:])
+    assert ("Error: %s %s: must be <= 2^28" % (field, value)).encode() in p.stderr, p.stderr[-500:]
+    assert not out.exists() and not (tmp_path / "out.html").exists()
+
+
+def test_cli_end_len_at_its_bound_is_any_end_len_beyond_the_reads(binary, small_input, tmp_path):
+    """-E 268435456 runs, and gives what -E 100000 gives: the end windows are the reads, there is no middle window."""
+    outs = []
+    for value in ("268435456", "100000", "150"):
+        out = tmp_path / ("out%s.fq" % value)
+        p = subprocess.run([binary, "-i", str(small_input / "in.fq"), "-a", str(small_input / "ad.fa"), "-o", str(out), "-x", "ont", "-5", "0", "-3", "0", "-E", value],
+                           capture_output=True, timeout=300)
+        assert p.returncode == 0, (value, p.returncode, p.stderr[-1000:])
+        outs.append(out.read_bytes())
+    assert outs[0] == outs[1] and outs[0].startswith(b"@") and outs[0] != outs[2]

@@ -1,7 +1,13 @@
 """The command line against the REFERENCE BINARY run side by side on freshly generated inputs and random flag
 sets (oracle/_ref/tgsfilter_ref: compiled from the reference where it lies, by `make -C oracle ref`; it travels
 to the GPU box with the repo).  Complements the committed goldens: nothing here was seen when the code was written.
-CPU: through the emulation build of the CLI (small inputs).  GPU (-m gpu): the real binary."""
+CPU: through the emulation build of the CLI (small inputs).  GPU (-m gpu): the real binary.
+
+The corners of the adapter search's parameters (test_cli_live_search_corners_emul: -E 0 .. 100 000, -T 0 .. 100 000, -m / -M
+around an adapter's length, 17 adapters by -a, which the reference takes -- it adds the reverse complements itself) pin the
+oracle's restatement to the reference where the reference can be asked.  It clamps -s and -S to at least 0.7 and 0.8:
+similarities below that are the C ABI's alone and are pinned to the oracle's restatement only (tests/search_domain.py).
+Six of these corners are also committed as goldens (tests/golden/search_*), for a box without the reference."""
 import os
 
 import numpy as np
@@ -62,6 +68,27 @@ def case(seed, n):
             for i in rng.choice(len(extra), int(rng.integers(1, 3)), replace=False):
                 adapters.append(extra[int(i)])
     return reads, flags, adapters, fasta
+
+
+SEARCH_17 = [synth.ONT_RAPID, synth.ONT_RAPID_RC, synth.PACBIO_BLUNT, synth.PACBIO_BLUNT_RC, b"AATGTACTTCGTTCAGTTACGTATTGCT", b"AGCAATACGTAACTGAACGAAGTACATT",
+             b"GCAATACGTAACTGAACGAAGT", b"ACTTCGTTCAGTTACGTATTGC", b"CTTGCGGGCGGCGGACTCTCCTCTGAAGATAGAGCGACAGGCAAG"] + \
+            [bytes(np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.default_rng(1700 + L).integers(0, 4, L)]) for L in (20, 31, 33, 64, 65, 91, 129, 150)]
+# (flags, adapters, qualities that read as Phred+64: with -E 100000 no read is long enough for the pre-pass to sample)
+SEARCH_CORNERS = [(["-E", e, "-T", t], [synth.ONT_RAPID], e == "100000") for e in ("0", "1", "5", "100000") for t in ("0", "1", "100000")] + \
+                 [(["-m", m, "-M", M], [synth.ONT_RAPID], False) for m, M in (("49", "49"), ("50", "50"), ("51", "51"), ("49", "51"), ("51", "50"))] + \
+                 [(["-M", "20", "-m", "12"], SEARCH_17, False), (["-E", "5", "-T", "1", "-M", "20"], SEARCH_17, False)]
+
+
+@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/tgsfilter_ref not built (make -C oracle ref)")
+@pytest.mark.parametrize("flags,adapters,phred64", SEARCH_CORNERS, ids=lambda v: "".join(v) if isinstance(v, list) and v and isinstance(v[0], str) else None)
+def test_cli_live_search_corners_emul(flags, adapters, phred64):
+    import subprocess
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tgsfilter_amd", "host"), "emul"], check=True)
+    reads = synth.make_reads(4242, 40, "ont", mean_len=1500, zoo=True, pmid=0.3)
+    if phred64:
+        reads = [(name, s, bytes(min(max(c, 33 + 16) + 31, 126) for c in q)) for name, s, q in reads]
+    common = ["-x", "ont", "-l", "100", "-5", "0", "-3", "0"] + ([] if phred64 else ["-q", "7"])
+    assert cli_check.compare_live(os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"), REF, reads, common + flags, adapters) != "both failed"
 
 
 def case2(seed, n):

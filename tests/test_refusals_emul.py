@@ -35,6 +35,10 @@ def test_emul_min_len_below_zero_is_refused_for_the_text_filter_too(emul):
     refusals.min_len_below_zero(emul, os.path.join(EMUL_DIR, "libtgsf_text_emul.so"))
 
 
+def test_emul_end_len_and_extra_len_above_their_bound_are_refused(emul):
+    refusals.end_len_and_extra_len_above_their_bound(emul)
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("at", [0, 7, 256, -1])
 @pytest.mark.parametrize("kind", ["len0", "offsets", "over"])

@@ -22,6 +22,10 @@ def test_gpu_min_len_below_zero_is_refused_for_the_text_filter_too():
     refusals.min_len_below_zero(None, None)
 
 
+def test_gpu_end_len_and_extra_len_above_their_bound_are_refused():
+    refusals.end_len_and_extra_len_above_their_bound(None)
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("at", [0, 7, 256, -1])
 @pytest.mark.parametrize("kind", ["len0", "offsets", "over"])

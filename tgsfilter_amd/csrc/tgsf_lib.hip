@@ -89,6 +89,7 @@ struct tgsf_ctx : rt_ctx {
 // ---------------------------------------------------------------------------
 // adapter tables
 // ---------------------------------------------------------------------------
+static const int kMaxLenParam = 1 << 28;      // the most end_len and extra_len may be: the cap on max_read_len (check_params)
 // What the kernels need to know of each adapter: lengths, thresholds, windows, gates.  No device call.
 static void adapter_rules(const tgsf_params& p, DevParams& P)
 {
@@ -109,7 +110,10 @@ static void adapter_rules(const tgsf_params& p, DevParams& P)
         // which no gate passes (:1246, :1283) -- the same outcome as reporting nothing.  Values below Q are unaffected.
         P.k_mid[a] = km > Q - 1 ? Q - 1 : km;             // (negative: see k_end_windows)
         P.k_end[a] = ke > Q - 1 ? Q - 1 : ke;
-        P.w5[a] = p.end_len + (int)((float)Q / p.end_sim);   // :1267 int(qLen / endSim), float division
+        // :1267 int(qLen / endSim), float division.  A quotient of 2^28 and beyond (a tiny end_sim) is not converted -- that is
+        // undefined -- but taken as 2^28: k_end_windows clamps the window to the read (:1268-1270), and no read is longer
+        const float w = (float)Q / p.end_sim;
+        P.w5[a] = p.end_len + (w < (float)kMaxLenParam ? (int)w : kMaxLenParam);
         // the similarity gates are monotone in mlen: evaluate the reference's float predicates here, once
         P.need_end[a] = P.need_mid[a] = Q + 1;                // Q+1: cannot pass (mlen <= Q)
         for (int m = Q; m >= 0; m--) {
@@ -327,6 +331,11 @@ static int check_params(const tgsf_params* p)
         return fail(nullptr, TGSF_E_UNSUPPORTED, "kmer (-k) %d: the repeat gate supports k-mer sizes 1..32 (the reference's k-mers are 64 bits)", p->kmer);
     // (a negative min_len lets a read shorter than its trims pass for a kept one in k_prepare's speculation: L - tail_trim is then formed in 32 unsigned bits)
     if (p->min_len < 0) return fail(nullptr, TGSF_E_INVALID, "min_len (-l) %d: must be >= 0", p->min_len);
+    // (end_len and extra_len above any read's length change nothing more -- the end windows are clamped to the read and there is no middle
+    // window -- but L - 2 * end_len, pos + end_len + 1 + extra_len and end_len + Q / end_sim are formed in 32 signed bits: bounded by the cap on
+    // max_read_len none of them wraps)
+    if (p->end_len > kMaxLenParam) return fail(nullptr, TGSF_E_INVALID, "end_len (-E) %d: must be <= 2^28", p->end_len);
+    if (p->extra_len > kMaxLenParam) return fail(nullptr, TGSF_E_INVALID, "extra_len (-T) %d: must be <= 2^28", p->extra_len);
     if (p->qtype != 33 && p->qtype != 64) return fail(nullptr, TGSF_E_INVALID, "qtype must be 33 or 64");
     if (p->bc_len < 0 || p->bc_len > kMaxBcLenTotal) return fail(nullptr, TGSF_E_INVALID, "bc_len (-e) outside [0,%d]", kMaxBcLenTotal);
     if (p->filter && p->n_adapters > 0) {

@@ -245,6 +245,10 @@ int parse_args(int argc, char** argv, Options& o)
     if (o.in_file.empty()) { std::cerr << "Error: lack argument for the must: -i " << std::endl; exit(-1); }
     if (access(o.in_file.c_str(), 0) != 0) { std::cerr << "Error: Can't find this file for -i " << o.in_file << std::endl; exit(-1); }
     if (o.only_qc) o.filter = false;
+    // tgsf_create's bounds on -E and -T (include/tgsf.h) in its own words, ahead of everything: the pre-pass forms
+    // 2 * max(-E, -e, 100) before a context with these values exists, and no output file is there yet to leave behind
+    if (o.end_len > (1 << 28)) { std::cerr << "Error: end_len (-E) " << o.end_len << ": must be <= 2^28" << std::endl; exit(-1); }
+    if (o.extra_len > (1 << 28)) { std::cerr << "Error: extra_len (-T) " << o.extra_len << ": must be <= 2^28" << std::endl; exit(-1); }
 
     if (o.filter) {
         if (o.read_type.empty()) { std::cerr << "Error: lack argument for the must: -x " << std::endl; exit(-1); }
