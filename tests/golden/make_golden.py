@@ -143,6 +143,15 @@ CASES.update({
     "search_a17": (dict(seed=47, n=40, kind="ont", mean_len=1500, zoo=True, pmid=0.3), SEARCH_17, "-x ont -l 100 -q 7 -5 0 -3 0 -M 20 -m 12"),
 })
 
+CASES.update({
+    # the quality gates on their seams (tests/quality_domain.py, cli_reads): reads whose mean -- raw, and of what a fixed trim, an end
+    # clip and a middle split keep -- is one sum below the flag's float32 value, on it where an integer sum gives it, and one above
+    # it; -q 7.5 (a mean can be 7.5), -q 9.9 (none is 9.9f: ten bytes that sum to 99 lie above it), -Q 12.25 with -q 0
+    "quality_q7.5": (dict(seed=48, n=1, kind="ont", mean_len=500), [synth.ONT_RAPID], "-x ont -l 100 -5 10 -3 7 -q 7.5", "fq", "quality:7.5:min"),
+    "quality_q9.9": (dict(seed=48, n=1, kind="ont", mean_len=500), [synth.ONT_RAPID], "-x hifi -l 100 -5 10 -3 7 -q 9.9", "fq", "quality:9.9:min"),
+    "quality_Q12.25": (dict(seed=48, n=1, kind="ont", mean_len=500), [synth.ONT_RAPID], "-x hifi -l 100 -5 10 -3 7 -q 0 -Q 12.25", "fq", "quality:12.25:max"),
+})
+
 IN_EXT = {"fq": "in.fq", "bam": "in.bam", "sam": "in.sam", "fa": "in.fa"}
 
 
@@ -165,6 +174,9 @@ def tweak(reads, how):
                 sq[pos:pos + len(m)] = m
             out.append((name, bytes(sq), q))
         return out
+    if how.startswith("quality:"):
+        from tests import quality_domain
+        return quality_domain.cli_reads(*how.split(":")[1:])
     if how == "odd_bytes":
         from tests import bytes_domain
         return bytes_domain.odd_bytes_into(reads, 41)

@@ -157,7 +157,9 @@ class GoldenCase:
 GOLDEN_CASES = ["ont_zoo", "ont_trim", "ont_discard", "hifi_zoo", "long_adapter", "ont_auto",
                 "hifi_auto", "qc_only", "ont_m1", "huge_adapter", "ont_phred64", "hifi_phred64_auto", "ont_e1300", "wide_adapter", "ont_high_qual", "giant_adapter", "odd_bytes",
                 # the adapter search on the corners of its parameters, and 17 adapters (tests/search_domain.py)
-                "search_E0", "search_E1", "search_E5", "search_m51", "search_E100000", "search_a17"]
+                "search_E0", "search_E1", "search_E5", "search_m51", "search_E100000", "search_a17",
+                # the quality gates with means on the thresholds, before the split and after it (tests/quality_domain.py, cli_reads)
+                "quality_q7.5", "quality_q9.9", "quality_Q12.25"]
 # whole-program cases that involve the host-side second pass (checked through the CLI only)
 # ... or a non-FASTQ input format (SAM / unaligned BAM decoded by the host; FASTA = records without qualities)
 GOLDEN_CLI_ONLY = ["ont_repeat", "repeat_k15", "repeat_k21", "repeat_k32", "repeat_k32b", "down_gd", "down_r", "down_R", "down_F", "hifi_bam", "ont_sam", "hifi_bam_auto",

@@ -7,13 +7,19 @@ The corners of the adapter search's parameters (test_cli_live_search_corners_emu
 around an adapter's length, 17 adapters by -a, which the reference takes -- it adds the reverse complements itself) pin the
 oracle's restatement to the reference where the reference can be asked.  It clamps -s and -S to at least 0.7 and 0.8:
 similarities below that are the C ABI's alone and are pinned to the oracle's restatement only (tests/search_domain.py).
-Six of these corners are also committed as goldens (tests/golden/search_*), for a box without the reference."""
+Six of these corners are also committed as goldens (tests/golden/search_*), for a box without the reference.
+
+The quality gates on their seams (test_cli_live_quality_corners_emul: -q and -Q of 7.5, 9.9, 12.25 and 20.3 over reads whose
+mean, or whose kept part's mean, is one sum below the flag's float, on it where that can be, and one above it:
+tests/quality_domain.py, cli_reads) pin the oracle's gate -- a double mean against the float threshold, both comparisons strict,
+before the split and after it -- to the reference's.  Three of them are committed as goldens (tests/golden/quality_*)."""
 import os
 
 import numpy as np
 import pytest
 
 from tests import cli_check
+from tests import quality_domain as qd
 from tgsfilter_amd import synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -89,6 +95,24 @@ def test_cli_live_search_corners_emul(flags, adapters, phred64):
         reads = [(name, s, bytes(min(max(c, 33 + 16) + 31, 126) for c in q)) for name, s, q in reads]
     common = ["-x", "ont", "-l", "100", "-5", "0", "-3", "0"] + ([] if phred64 else ["-q", "7"])
     assert cli_check.compare_live(os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"), REF, reads, common + flags, adapters) != "both failed"
+
+
+QUALITY_CORNERS = qd.CLI_CORNERS        # (the flag's value, which gate it sets, the read type)
+
+
+def quality_flags(value, side, kind):
+    """-5 10 -3 7 and an adapter: the gate after the split is reached by a fixed trim, an end clip and a middle split.  (-q 0
+    beside a -Q: without a -q the reference chooses one from the read type, above the means these reads are built to have.)"""
+    return ["-x", kind, "-l", "100", "-5", "10", "-3", "7"] + (["-q", value] if side == "min" else ["-q", "0", "-Q", value])
+
+
+@pytest.mark.skipif(not os.path.exists(REF), reason="oracle/_ref/tgsfilter_ref not built (make -C oracle ref)")
+@pytest.mark.parametrize("value,side,kind", QUALITY_CORNERS)
+def test_cli_live_quality_corners_emul(value, side, kind):
+    import subprocess
+    subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tgsfilter_amd", "host"), "emul"], check=True)
+    reads = qd.cli_case(value, side, kind)          # (asserted on the oracle first: each read is kept as the pieces it is designed for)
+    assert cli_check.compare_live(os.path.join(ROOT, "tests", "emul", "tgsfilter_emul"), REF, reads, quality_flags(value, side, kind), [synth.ONT_RAPID]) != "both failed"
 
 
 def case2(seed, n):
