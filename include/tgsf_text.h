@@ -30,6 +30,9 @@
  * THE OUTPUT SIDE (tgsf_text_format*, tgsf_text_filter, further down): the records the filter kept, formatted as clean
  * FASTQ / FASTA text on the device, from the text, the index and the filter's fragment table, all of which sit in HBM already.
  *
+ * THE BAM INPUT SIDE (tgsf_text_bam_*, at the end, with its rule): inflated unaligned BAM records are decoded on the device
+ * into the object's text buffer as FASTQ text, with the same index; from there everything above works unchanged.
+ *
  * Conventions as in tgsf.h: plain C, 0 or a negative tgsf_status; calls on one object are serialised by the caller,
  * different objects may be driven from different threads.  No CPU fallback.
  */
@@ -231,6 +234,110 @@ int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t
 /* Milliseconds of the last format's three stages -- sizes (flags, their sums, sizes), layout (the sums of the sizes, the
  * record ends), copy -- when tgsf_text_profile was on; waits for that format to finish. */
 int tgsf_text_out_stage_ms(tgsf_text* tx, float ms[3]);
+
+/*
+ * ---- the BAM input side: inflated unaligned BAM records in, FASTQ text and its index out ------------------------------
+ *
+ * THE RULE.  Truth is decode_bam of the command line (tgsfilter_amd/host/bam.cpp, a restatement of the reference's sam_read1
+ * loop).  The input is a chunk of INFLATED BAM bytes (BGZF inflation is the caller's) that begins at a record's block_size
+ * field -- behind the BAM header (tgsf_text_bam_header) or at an earlier call's `consumed` -- and ends at any byte.
+ *
+ *   - The record at byte `at`: block_size is the little-endian u32 there, the record the block_size bytes behind it; it is
+ *     COMPLETE when at + 4 + block_size <= n_bytes.  l_read_name is its byte 8, n_cigar_op the u16 at byte 12, l_seq the u32
+ *     at byte 16, the name starts at byte 32; o_seq = 32 + l_read_name + 4 * n_cigar_op, o_qual = o_seq + (l_seq + 1) / 2.
+ *     It is REGULAR when block_size >= 32, o_qual + l_seq <= block_size (in 64 bits) and l_seq > 0.  The name is the bytes from
+ *     byte 32 to the first NUL within l_read_name (strnlen; it may be empty).  The flag word, the CIGAR and the auxiliary
+ *     fields are skipped, as by the host: reads are never reverse-complemented.
+ *   - The decoded text is the concatenation, in input order, of one piece per indexed record:
+ *         '@' name '\n' bases '\n' '+' '\n' quals '\n'
+ *     bases[k] = T[nibble k] (even k: the high nibble) with the host's and the reference's table (src/TGSFilter.cpp:31)
+ *     T = {0,'A','C',0,'G',0,0,0,'T',0,0,0,0,0,0,'N'}: of the codes of "=ACMGRSVTWYHKDBN" only A, C, G, T and N keep a letter,
+ *     every other code becomes a NUL byte, as in the reference's output.  quals[k] = (uint8_t)(q[k] + 33): an absent quality
+ *     string (all 0xFF) becomes spaces, exactly as in the host.
+ *   - The index is the five arrays of tgsf_text_index_arrays with offsets into the decoded text: name_off behind the '@',
+ *     seq_off = name_off + name_len + 1, qual_off = seq_off + len + 3, len = l_seq.  After a decode the object is in exactly
+ *     the state tgsf_text_index_device leaves it in on the same FASTQ text: tgsf_submit_device, tgsf_text_format* and
+ *     tgsf_text_buffers work on it unchanged.
+ *   - Indexed is the LONGEST PREFIX OF COMPLETE, REGULAR RECORDS of at most max_records records whose decoded text has at
+ *     most max_bytes bytes.  `consumed` is the byte offset of the first record not indexed.
+ *   - stop: TGSF_TEXT_END -- nothing is left, or a non-final chunk ends inside a record or inside its block_size (that tail
+ *     belongs to the next chunk).  TGSF_TEXT_IRREGULAR -- the record at `consumed` is not regular, or the chunk is final and
+ *     the bytes left (1 or more) make no complete record (the host ends its stream silently there, or dies on l_seq == 0:
+ *     what to say is the caller's business, as with text).  TGSF_TEXT_CAPACITY -- max_records are indexed and bytes are
+ *     left, or the next record's text does not fit max_bytes (n_records may then be 0: one record larger than the object).
+ *   - A quality byte of 233 decodes to '\n'; the host refuses the whole input ("unsupported quality value in NAME").  Here
+ *     bad_qual is the LOWEST index of an indexed record with such a byte (UINT32_MAX: none) and the text is written as the
+ *     rule says; tgsf_text_bam_submit / _filter then return TGSF_E_DATA, naming the record, and the filter does not run.
+ *
+ * The chain of block_size fields is a dependent load per record: it is walked on the host (tgsf_text_bam_walk, O(records)).
+ * Everything a position can check on its own -- the field overrun, l_seq == 0, the name's NUL, the text capacity -- and every
+ * byte of the text is the device's.
+ */
+
+/* 48 bytes */
+typedef struct tgsf_text_bam_summary {
+    uint32_t n_records;
+    uint32_t stop;         /* TGSF_TEXT_*                                                                    */
+    uint64_t consumed;     /* the byte offset, in the chunk, of the first record that is not indexed          */
+    uint64_t text_bytes;   /* bytes of the decoded text (TGSF_TEXT_PAD zeros follow them in the buffer)       */
+    uint64_t bases;        /* sum of len over the index                                                       */
+    uint32_t longest;      /* largest len                                                                     */
+    uint32_t bad_qual;     /* the lowest indexed record with a quality byte of 233; UINT32_MAX: none          */
+    float    device_ms;    /* the decode kernels by HIP events, when tgsf_text_profile is on and the call synchronises
+                              (tgsf_text_bam_decode, _submit, _filter); else 0                                */
+    uint32_t reserved;
+} tgsf_text_bam_summary;
+
+/* Host only.  bam[0 .. n_bytes) begins with the BAM header: checks the magic "BAM\1", steps over l_text, the text and the
+ * reference list; *records_at becomes the offset of the first record's block_size.  TGSF_E_DATA when the magic is wrong or
+ * the header is not complete within n_bytes (tgsf_text_last_error(NULL) says which). */
+int tgsf_text_bam_header(const uint8_t* bam, uint64_t n_bytes, uint64_t* records_at);
+
+/*
+ * Host only: the chain walk.  It reads block_size alone.  rec_off (room for max_records + 1 entries) takes the offsets of
+ * the records walked and, as entry *n, the offset behind the last of them (= *consumed).  It stops on block_size < 32
+ * (TGSF_TEXT_IRREGULAR), on an incomplete record or fewer than 4 bytes (final: TGSF_TEXT_IRREGULAR, else TGSF_TEXT_END),
+ * at max_records with bytes left (TGSF_TEXT_CAPACITY) or at n_bytes (TGSF_TEXT_END).
+ */
+int tgsf_text_bam_walk(const uint8_t* bam, uint64_t n_bytes, int final, uint32_t max_records, uint64_t* rec_off, uint32_t* n,
+                       uint32_t* stop, uint64_t* consumed);
+
+/*
+ * Once, before the first decode: the device buffer for chunks of up to max_bam_bytes BAM bytes (16-byte aligned, padded), the
+ * record-offset table (max_records + 1) and the per-record scratch.  No later call allocates.  A decode before it is
+ * TGSF_E_INVALID, a second call is TGSF_E_INVALID, a chunk of n_bytes > max_bam_bytes TGSF_E_CAPACITY before anything is copied.
+ */
+int tgsf_text_bam_reserve(tgsf_text* tx, uint64_t max_bam_bytes);
+
+/*
+ * BAM bytes in HOST memory: the walk, the bytes and the offsets go up, the text is decoded into the object's own text buffer
+ * (TGSF_TEXT_PAD zeros behind it) and its index arrays; the summary and, if wanted, the index come down.
+ */
+int tgsf_text_bam_decode(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, const tgsf_text_index_arrays* out_index,
+                         tgsf_text_bam_summary* out_summary);
+
+/*
+ * The BAM bytes in HBM already (d_bam NULL: the object's buffer); rec_off[0 .. n_walked] and walk_stop are the HOST results of
+ * tgsf_text_bam_walk on the same bytes (trusted, as tgsf.h trusts offsets: every walked record is complete and has
+ * block_size >= 32; n_walked <= max_records).  Everything is enqueued on `hip_stream` (NULL: the object's own) and nothing is
+ * waited for.  The text always goes to the object's text buffer; d_index NULL: the object's index arrays; d_summary NULL: the
+ * object's own.  Bytes of d_bam at and behind n_bytes are never read.  The scratch is the object's: one call at a time, or
+ * all on one stream.
+ */
+int tgsf_text_bam_decode_device(tgsf_text* tx, const uint8_t* d_bam, uint64_t n_bytes, int final, const uint64_t* rec_off,
+                                uint32_t n_walked, uint32_t walk_stop, const tgsf_text_index_arrays* d_index,
+                                tgsf_text_bam_summary* d_summary, void* hip_stream);
+
+/*
+ * tgsf_text_submit / tgsf_text_filter with the decode in place of upload plus index: fasta = 0, the batch's n_bytes is
+ * text_bytes.  What libtgsf refuses is handed through unchanged; bad_qual set: TGSF_E_DATA (out_summary / in_summary are
+ * filled), the filter has not run, the object stays usable.  fastq_out 0 and 1 both work.
+ */
+int tgsf_text_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final,
+                         const tgsf_text_index_arrays* out_index, tgsf_text_bam_summary* out_summary, tgsf_batch_out* batch_out);
+int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
+                         uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                         tgsf_text_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,18 @@ struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exa
     uint64_t* d_orec_end = nullptr;
     uint8_t* d_out = nullptr;
     tgsf_text_out_summary* d_osummary = nullptr;
+    // the BAM input side (tgsf_text_bam_reserve): the chunk's bytes, the walked records' offsets, per-record scratch
+    bool bam_reserved = false;
+    uint64_t max_bam = 0;
+    uint8_t* d_bam = nullptr;           // max_bam rounded up to 16, + TGSF_TEXT_PAD
+    uint64_t* d_brec_off = nullptr;     // max_records + 1
+    uint64_t* d_bsize = nullptr;        // sizes of the records' text -> exclusive sums within blocks of kTextScanTile records
+    uint64_t* d_bsize_part = nullptr;   // ... and the blocks' offsets
+    uint64_t* d_bends = nullptr;        // the byte behind each record's text
+    uint32_t* d_boseq = nullptr;        // where the packed bases begin in each record
+    BamState* d_bstate = nullptr;
+    tgsf_text_bam_summary* d_bsummary = nullptr;
+    std::vector<uint64_t> h_rec_off;    // the walk of tgsf_text_bam_decode / _submit / _filter
     // around the last index, and around the stages of the last format (profile)
     rt_event ev[2] = {nullptr, nullptr};
     bool ev_recorded = false;
@@ -265,6 +277,48 @@ extern "C" int tgsf_text_index(tgsf_text* tx, const uint8_t* text, uint64_t n_by
     return fetch(tx, out_index, out_summary, &sum);
 }
 
+// The filter on the text and the index that are in the object (n_records of them, n_bytes of text), through ctx; bo == NULL:
+// nothing comes down.  The fragments go to d_fr on the device (room for fr_cap; NULL: not wanted), their number to *n_frags.
+static int run_filter(tgsf_text* tx, tgsf_ctx* ctx, uint32_t n_records, uint64_t n_bytes, tgsf_batch_out* bo, tgsf_fragment* d_fr,
+                      uint32_t fr_cap, uint32_t* n_frags)
+{
+    int e;
+    if (bo) bo->n_frags = 0;
+    *n_frags = 0;
+    if (n_records) {
+        tgsf_batch_in in;
+        memset(&in, 0, sizeof in);
+        in.seq = tx->d_text;
+        in.qual = tx->d_text;
+        in.offsets = tx->d_index.seq_off;
+        in.lengths = tx->d_index.len;
+        in.qual_offsets = tx->d_index.qual_off;
+        in.n_reads = n_records;
+        in.n_bytes = n_bytes;
+        tgsf_batch_out dout;
+        dout.reads = tx->d_reads;
+        dout.frags = d_fr;
+        dout.frag_capacity = d_fr ? fr_cap : 0u;
+        dout.n_frags = 0;
+        e = tgsf_submit_device(ctx, &in, &dout, tx->d_nfrags, (void*)tx->stream);
+        if (!e) e = tgsf_wait(ctx);
+        if (e) return fail(tx, e, "libtgsf: %s", tgsf_last_error(ctx));
+        uint32_t nf = 0;
+        int he = rt_d2h(&nf, tx->d_nfrags, 4, tx->stream);
+        if (bo) he |= rt_d2h(bo->reads, tx->d_reads, (size_t)n_records * sizeof(tgsf_read_result), tx->stream);
+        if (!he) he = rt_sync(tx->stream);
+        if (!he && nf > dout.frag_capacity) return fail(tx, TGSF_E_CAPACITY, "batch produced %u fragments, caller provided room for %u", nf, dout.frag_capacity);
+        if (!he && nf && bo && bo->frags) {
+            he = rt_d2h(bo->frags, d_fr, (size_t)nf * sizeof(tgsf_fragment), tx->stream);
+            if (!he) he = rt_sync(tx->stream);
+        }
+        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+        if (bo) bo->n_frags = nf;
+        *n_frags = nf;
+    }
+    return TGSF_OK;
+}
+
 // tgsf_text_submit; bo == NULL (tgsf_text_filter only): nothing but the summary comes down.  The fragments go to d_fr on the
 // device (room for fr_cap; NULL: not wanted), their number to *n_frags.
 static int submit_core(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
@@ -277,39 +331,7 @@ static int submit_core(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64
     tgsf_text_summary sum;
     // the one wait between the index and the filter: libtgsf sizes its launches by n_reads on the host
     if ((e = fetch(tx, nullptr, nullptr, &sum))) return e;
-    if (bo) bo->n_frags = 0;
-    *n_frags = 0;
-    if (sum.n_records) {
-        tgsf_batch_in in;
-        memset(&in, 0, sizeof in);
-        in.seq = tx->d_text;
-        in.qual = tx->d_text;
-        in.offsets = tx->d_index.seq_off;
-        in.lengths = tx->d_index.len;
-        in.qual_offsets = tx->d_index.qual_off;
-        in.n_reads = sum.n_records;
-        in.n_bytes = n_bytes;
-        tgsf_batch_out dout;
-        dout.reads = tx->d_reads;
-        dout.frags = d_fr;
-        dout.frag_capacity = d_fr ? fr_cap : 0u;
-        dout.n_frags = 0;
-        e = tgsf_submit_device(ctx, &in, &dout, tx->d_nfrags, (void*)tx->stream);
-        if (!e) e = tgsf_wait(ctx);
-        if (e) return fail(tx, e, "libtgsf: %s", tgsf_last_error(ctx));
-        uint32_t nf = 0;
-        int he = rt_d2h(&nf, tx->d_nfrags, 4, tx->stream);
-        if (bo) he |= rt_d2h(bo->reads, tx->d_reads, (size_t)sum.n_records * sizeof(tgsf_read_result), tx->stream);
-        if (!he) he = rt_sync(tx->stream);
-        if (!he && nf > dout.frag_capacity) return fail(tx, TGSF_E_CAPACITY, "batch produced %u fragments, caller provided room for %u", nf, dout.frag_capacity);
-        if (!he && nf && bo && bo->frags) {
-            he = rt_d2h(bo->frags, d_fr, (size_t)nf * sizeof(tgsf_fragment), tx->stream);
-            if (!he) he = rt_sync(tx->stream);
-        }
-        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-        if (bo) bo->n_frags = nf;
-        *n_frags = nf;
-    }
+    if ((e = run_filter(tx, ctx, sum.n_records, n_bytes, bo, d_fr, fr_cap, n_frags))) return e;
     // the index last: the filter does not wait for it
     tgsf_text_summary again;
     if (out_index && (e = fetch(tx, out_index, nullptr, &again))) return e;
@@ -520,6 +542,234 @@ extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* tex
     memset(out_summary, 0, sizeof *out_summary);
     if ((e = submit_core(tx, ctx, text, n_bytes, fasta, final, out_index, in_summary, bo, d_fr, down ? bo->frag_capacity : tx->max_frags, &nf))) return e;
     if (!in_summary->n_records) return TGSF_OK;                        // nothing ran: an empty output, no error
+    if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
+    return format_down(tx, tx->d_reads, d_fr, nf, fastq_out, out, out_capacity, rec_end, out_summary);
+}
+
+// ---- the BAM input side --------------------------------------------------------------------------------------------------
+extern "C" int tgsf_text_bam_header(const uint8_t* bam, uint64_t n_bytes, uint64_t* records_at)
+{
+    if (!records_at || (!bam && n_bytes)) return fail(nullptr, TGSF_E_INVALID, "null argument");
+    *records_at = 0;
+    uint64_t at = 4;
+    auto need = [&](uint64_t k) { return at + k <= n_bytes; };
+    if (n_bytes < 4) return fail(nullptr, TGSF_E_DATA, "truncated BAM header: %llu bytes", (unsigned long long)n_bytes);
+    if (memcmp(bam, "BAM\1", 4) != 0) return fail(nullptr, TGSF_E_DATA, "not BAM: the magic \"BAM\\1\" is missing");
+    if (!need(4)) return fail(nullptr, TGSF_E_DATA, "truncated BAM header: l_text is not complete");
+    const uint32_t l_text = bam_le32(bam + at); at += 4;
+    if (!need((uint64_t)l_text + 4)) return fail(nullptr, TGSF_E_DATA, "truncated BAM header: %u bytes of text are not complete", l_text);
+    at += l_text;
+    const uint32_t n_ref = bam_le32(bam + at); at += 4;
+    for (uint32_t i = 0; i < n_ref; i++) {
+        if (!need(4)) return fail(nullptr, TGSF_E_DATA, "truncated BAM reference list: entry %u of %u", i, n_ref);
+        const uint32_t l_name = bam_le32(bam + at); at += 4;
+        if (!need((uint64_t)l_name + 4)) return fail(nullptr, TGSF_E_DATA, "truncated BAM reference list: entry %u of %u", i, n_ref);
+        at += (uint64_t)l_name + 4;
+    }
+    *records_at = at;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bam_walk(const uint8_t* bam, uint64_t n_bytes, int final, uint32_t max_records, uint64_t* rec_off, uint32_t* n,
+                                  uint32_t* stop, uint64_t* consumed)
+{
+    if (!rec_off || !n || !stop || !consumed || (!bam && n_bytes)) return fail(nullptr, TGSF_E_INVALID, "null argument");
+    if (final != 0 && final != 1) return fail(nullptr, TGSF_E_INVALID, "final is 0 or 1");
+    uint64_t at = 0;
+    uint32_t k = 0, why = TGSF_TEXT_END;
+    for (;;) {
+        rec_off[k] = at;
+        if (at == n_bytes) break;                                      // nothing is left
+        if (k == max_records) { why = TGSF_TEXT_CAPACITY; break; }
+        if (n_bytes - at < 4) { why = final ? TGSF_TEXT_IRREGULAR : TGSF_TEXT_END; break; }
+        const uint32_t block = bam_le32(bam + at);
+        if (block < 32u) { why = TGSF_TEXT_IRREGULAR; break; }
+        if (n_bytes - at - 4 < block) { why = final ? TGSF_TEXT_IRREGULAR : TGSF_TEXT_END; break; }
+        at += 4ull + block;
+        k++;
+    }
+    *n = k;
+    *stop = why;
+    *consumed = at;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bam_reserve(tgsf_text* tx, uint64_t max_bam_bytes)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (tx->bam_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bam_reserve has been called already (%llu bytes of BAM)", (unsigned long long)tx->max_bam);
+    if (max_bam_bytes == 0) return fail(tx, TGSF_E_INVALID, "max_bam_bytes must be positive");
+    (void)rt_set_device(tx->device);
+    const size_t m = tx->max_records;
+    int e = 0;
+    e |= dev_alloc(tx, &tx->d_bam, ((max_bam_bytes + 15u) & ~15ull) + TGSF_TEXT_PAD);
+    if (!e) e |= dev_alloc(tx, &tx->d_brec_off, m + 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_bsize, m);
+    if (!e) e |= dev_alloc(tx, &tx->d_bsize_part, m / kTextScanTile + 2);
+    if (!e) e |= dev_alloc(tx, &tx->d_bends, m);
+    if (!e) e |= dev_alloc(tx, &tx->d_boseq, m);
+    if (!e) e |= dev_alloc(tx, &tx->d_bstate, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_bsummary, 1);
+    if (e) return fail(tx, TGSF_E_HIP, "device allocation failed (%llu bytes of BAM, %u records)", (unsigned long long)max_bam_bytes, tx->max_records);
+    tx->h_rec_off.resize(m + 1);
+    tx->max_bam = max_bam_bytes;
+    tx->bam_reserved = true;
+    return TGSF_OK;
+}
+
+// what every decode is refused for before anything is copied or enqueued
+static int check_bam(tgsf_text* tx, uint64_t n_bytes, int final)
+{
+    if (!tx->bam_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bam_reserve has not been called on this object: no buffers to decode with");
+    if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
+    if (n_bytes > tx->max_bam)
+        return fail(tx, TGSF_E_CAPACITY, "BAM chunk of %llu bytes, the object was reserved for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_bam);
+    return TGSF_OK;
+}
+
+// the offsets up and the eight launches of one decode, on st; nothing is waited for
+static int enqueue_bam(tgsf_text* tx, const uint8_t* d_bam, const uint64_t* rec_off, uint32_t n_walked, uint32_t walk_stop,
+                       const tgsf_text_index_arrays& I, tgsf_text_bam_summary* d_summary, rt_stream st)
+{
+    const uint64_t n = n_walked;
+    const uint32_t nb = (uint32_t)((n + kTextScanTile - 1) / kTextScanTile);
+    const unsigned grec = grid_cap(std::min(std::max(blocks_for(n, kTextThreads), 1u), 2048u));
+    const unsigned gfold = std::min(grec, 64u);                                    // every wave ends in two atomics on one word each
+    // a wave per 4 KiB piece of the text, as many as the object's buffer has, at most a few per SIMD of the device: they stride
+    const unsigned gtext = grid_cap(std::min(std::max(blocks_for(((tx->max_bytes + TGSF_TEXT_PAD + kTextPiece - 1) / kTextPiece) * kTextLanes, kTextThreads), 1u), 2048u));
+    const int he = rt_h2d(tx->d_brec_off, rec_off, (size_t)(n + 1) * 8, st);
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    BamState* S = tx->d_bstate;
+    if (tx->profile) (void)rt_event_record(tx->ev[0], st);
+    TGSF_LAUNCH_COOP(k_bam_reset, 1, 64, st, S);
+    if (n) {
+        TGSF_LAUNCH(k_bam_heads, grec, kTextThreads, st, d_bam, (const uint64_t*)tx->d_brec_off, n_walked, tx->d_bsize, tx->d_boseq, I, S);
+        TGSF_LAUNCH_COOP(k_textout_scan_tiles64, nb, 256, st, tx->d_bsize, n, tx->d_bsize_part);
+        TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_bsize_part, nb, &S->total);
+        TGSF_LAUNCH(k_bam_layout, grec, kTextThreads, st, (const uint64_t*)tx->d_bsize, (const uint64_t*)tx->d_bsize_part, n_walked, tx->max_bytes, S,
+                    tx->d_bends, I);
+        TGSF_LAUNCH(k_bam_fold, gfold, kTextThreads, st, (const uint32_t*)I.len, n_walked, S);
+    }
+    TGSF_LAUNCH_COOP(k_bam_finish, 1, 64, st, (const uint64_t*)tx->d_brec_off, (const uint64_t*)tx->d_bends, n_walked, walk_stop, (const BamState*)S, d_summary);
+    TGSF_LAUNCH(k_bam_unpack, gtext, kTextThreads, st, d_bam, (const uint64_t*)tx->d_brec_off, (const uint32_t*)tx->d_boseq, I,
+                (const uint64_t*)tx->d_bends, d_summary, tx->d_text);
+    if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bam_decode_device(tgsf_text* tx, const uint8_t* d_bam, uint64_t n_bytes, int final, const uint64_t* rec_off,
+                                           uint32_t n_walked, uint32_t walk_stop, const tgsf_text_index_arrays* d_index,
+                                           tgsf_text_bam_summary* d_summary, void* hip_stream)
+{
+    if (!tx) return TGSF_E_INVALID;
+    int e = check_bam(tx, n_bytes, final);
+    if (e) return e;
+    if (!rec_off) return fail(tx, TGSF_E_INVALID, "null argument: the record offsets of tgsf_text_bam_walk");
+    if (walk_stop > TGSF_TEXT_CAPACITY) return fail(tx, TGSF_E_INVALID, "walk_stop is one of TGSF_TEXT_END, _IRREGULAR, _CAPACITY");
+    if (n_walked > tx->max_records) return fail(tx, TGSF_E_CAPACITY, "%u records walked, the object was created for %u", n_walked, tx->max_records);
+    if (rec_off[n_walked] > n_bytes) return fail(tx, TGSF_E_INVALID, "the record offsets end at byte %llu of %llu", (unsigned long long)rec_off[n_walked], (unsigned long long)n_bytes);
+    if ((e = check_index(tx, d_index))) return e;
+    (void)rt_set_device(tx->device);
+    return enqueue_bam(tx, d_bam ? d_bam : tx->d_bam, rec_off, n_walked, walk_stop, d_index ? *d_index : tx->d_index,
+                       d_summary ? d_summary : tx->d_bsummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
+}
+
+// walk, upload, decode on the object's stream; the summary comes down (the one wait)
+static int bam_decode_down(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, tgsf_text_bam_summary* sum)
+{
+    uint32_t n_walked = 0, walk_stop = 0;
+    uint64_t consumed = 0;
+    int e = tgsf_text_bam_walk(bam, n_bytes, final, tx->max_records, tx->h_rec_off.data(), &n_walked, &walk_stop, &consumed);
+    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
+    int he = n_bytes ? rt_h2d(tx->d_bam, bam, n_bytes, tx->stream) : 0;
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    if ((e = enqueue_bam(tx, tx->d_bam, tx->h_rec_off.data(), n_walked, walk_stop, tx->d_index, tx->d_bsummary, tx->stream))) return e;
+    he = rt_d2h(sum, tx->d_bsummary, sizeof *sum, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    sum->device_ms = index_ms(tx);
+    return TGSF_OK;
+}
+
+static int fetch_index(tgsf_text* tx, const tgsf_text_index_arrays* out_index, size_t k)
+{
+    if (!out_index || !k) return TGSF_OK;
+    int he = 0;
+    if (out_index->seq_off) he |= rt_d2h(out_index->seq_off, tx->d_index.seq_off, k * 8, tx->stream);
+    if (out_index->qual_off) he |= rt_d2h(out_index->qual_off, tx->d_index.qual_off, k * 8, tx->stream);
+    if (out_index->len) he |= rt_d2h(out_index->len, tx->d_index.len, k * 4, tx->stream);
+    if (out_index->name_off) he |= rt_d2h(out_index->name_off, tx->d_index.name_off, k * 8, tx->stream);
+    if (out_index->name_len) he |= rt_d2h(out_index->name_len, tx->d_index.name_len, k * 4, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    return he ? fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he)) : TGSF_OK;
+}
+
+extern "C" int tgsf_text_bam_decode(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, const tgsf_text_index_arrays* out_index,
+                                    tgsf_text_bam_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!out_summary || (!bam && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_bam(tx, n_bytes, final);
+    if (e) return e;
+    (void)rt_set_device(tx->device);
+    tgsf_text_bam_summary sum;
+    if ((e = bam_decode_down(tx, bam, n_bytes, final, &sum))) return e;
+    if ((e = fetch_index(tx, out_index, sum.n_records))) return e;
+    *out_summary = sum;
+    return TGSF_OK;
+}
+
+// the host refuses the whole input for a quality that decodes to '\n'; here the call, naming the record as the host does
+static int bad_quality(tgsf_text* tx, const uint8_t* bam, const tgsf_text_bam_summary& sum)
+{
+    const uint8_t* r = bam + tx->h_rec_off[sum.bad_qual] + 4;
+    const char* name = reinterpret_cast<const char*>(r + 32);
+    return fail(tx, TGSF_E_DATA, "unsupported quality value in %.*s (record %u of the chunk): the filter has not run", (int)strnlen(name, r[8]), name, sum.bad_qual);
+}
+
+extern "C" int tgsf_text_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final,
+                                    const tgsf_text_index_arrays* out_index, tgsf_text_bam_summary* out_summary, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !bo || !bo->reads || (!bam && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_bam(tx, n_bytes, final);
+    if (e) return e;
+    (void)rt_set_device(tx->device);
+    if ((e = grow_frags(tx, bo))) return e;
+    tgsf_text_bam_summary sum;
+    if ((e = bam_decode_down(tx, bam, n_bytes, final, &sum))) return e;
+    *out_summary = sum;
+    bo->n_frags = 0;
+    if (sum.bad_qual != 0xFFFFFFFFu) return bad_quality(tx, bam, sum);
+    uint32_t nf = 0;
+    if ((e = run_filter(tx, ctx, sum.n_records, sum.text_bytes, bo, bo->frags ? tx->d_frags : nullptr, bo->frags ? bo->frag_capacity : 0u, &nf))) return e;
+    return fetch_index(tx, out_index, sum.n_records);                  // the index last: the filter does not wait for it
+}
+
+extern "C" int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
+                                    uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                                    tgsf_text_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!bam && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, 0, fastq_out);
+    if (!e) e = check_bam(tx, n_bytes, final);
+    if (e) return e;
+    (void)rt_set_device(tx->device);
+    const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts, as in tgsf_text_bam_submit
+    if (down && (e = grow_frags(tx, bo))) return e;
+    tgsf_fragment* d_fr = down ? tx->d_frags : tx->d_ofrags;
+    memset(out_summary, 0, sizeof *out_summary);
+    tgsf_text_bam_summary sum;
+    if ((e = bam_decode_down(tx, bam, n_bytes, final, &sum))) return e;
+    *in_summary = sum;
+    if (bo) bo->n_frags = 0;
+    if (sum.bad_qual != 0xFFFFFFFFu) return bad_quality(tx, bam, sum);
+    uint32_t nf = 0;
+    if ((e = run_filter(tx, ctx, sum.n_records, sum.text_bytes, bo, d_fr, down ? bo->frag_capacity : tx->max_frags, &nf))) return e;
+    if ((e = fetch_index(tx, out_index, sum.n_records))) return e;
+    if (!sum.n_records) return TGSF_OK;                                // nothing ran: an empty output, no error
     if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
     return format_down(tx, tx->d_reads, d_fr, nf, fastq_out, out, out_capacity, rec_end, out_summary);
 }

@@ -5,6 +5,9 @@
     idx, summary, reads, frags = tx.submit(ctx, text)   # text in, filter results out (ctx: capi.Context)
     tx.reserve_output(max_frags, max_out_bytes)         # once; then
     clean, rec_end, out_summary, summary = tx.filter(ctx, text)   # text in, clean FASTQ / FASTA text out
+    tx.reserve_bam(max_bam_bytes)                       # once; then, for inflated unaligned BAM from bam_header()'s offset on,
+    idx, bam_summary = tx.bam_decode(bam)               # the records as FASTQ text in the object, and its index
+    clean, rec_end, out_summary, bam_summary = tx.bam_filter(ctx, bam)   # BAM in, clean text out
 
 There is no CPU fallback: the library found beside this file must be the HIP build.  (tests/emul builds a serial
 emulation of the same kernels; only tests pass its path in.)
@@ -33,6 +36,8 @@ SYMBOLS = [
     "tgsf_text_abi_version", "tgsf_text_backend", "tgsf_text_create", "tgsf_text_destroy", "tgsf_text_last_error", "tgsf_text_profile",
     "tgsf_text_buffers", "tgsf_text_index", "tgsf_text_upload", "tgsf_text_index_device", "tgsf_text_fetch", "tgsf_text_submit",
     "tgsf_text_out_reserve", "tgsf_text_format_device", "tgsf_text_format", "tgsf_text_filter", "tgsf_text_out_stage_ms",
+    "tgsf_text_bam_header", "tgsf_text_bam_walk", "tgsf_text_bam_reserve", "tgsf_text_bam_decode", "tgsf_text_bam_decode_device",
+    "tgsf_text_bam_submit", "tgsf_text_bam_filter",
 ]
 
 
@@ -62,7 +67,18 @@ class OutSummary(C.Structure):
         return {"n_bytes": self.n_bytes, "bases": self.bases, "n_records": self.n_records, "stop": self.stop, "device_ms": self.device_ms}
 
 
+class BamSummary(C.Structure):
+    _fields_ = [("n_records", C.c_uint32), ("stop", C.c_uint32), ("consumed", C.c_uint64), ("text_bytes", C.c_uint64), ("bases", C.c_uint64),
+                ("longest", C.c_uint32), ("bad_qual", C.c_uint32), ("device_ms", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"n_records": self.n_records, "stop": self.stop, "consumed": self.consumed, "text_bytes": self.text_bytes, "bases": self.bases,
+                "longest": self.longest, "bad_qual": self.bad_qual, "device_ms": self.device_ms, "reserved": self.reserved}
+
+
+NO_BAD_QUAL = 0xFFFFFFFF
 assert C.sizeof(Summary) == 32
+assert C.sizeof(BamSummary) == 48
 assert C.sizeof(OutSummary) == 32
 
 Index = namedtuple("Index", "seq_off qual_off len name_off name_len")
@@ -99,6 +115,14 @@ def load(path: str | None = None):
         L.tgsf_text_filter.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, vp, C.POINTER(OutSummary), C.POINTER(Summary),
                                        C.POINTER(IndexArrays), C.POINTER(abi.BatchOut)]
         L.tgsf_text_out_stage_ms.argtypes = [vp, C.POINTER(C.c_float * 3)]
+        L.tgsf_text_bam_header.argtypes = [vp, u64, C.POINTER(u64)]
+        L.tgsf_text_bam_walk.argtypes = [vp, u64, i, u32, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
+        L.tgsf_text_bam_reserve.argtypes = [vp, u64]
+        L.tgsf_text_bam_decode.argtypes = [vp, vp, u64, i, C.POINTER(IndexArrays), C.POINTER(BamSummary)]
+        L.tgsf_text_bam_decode_device.argtypes = [vp, vp, u64, i, vp, u32, u32, C.POINTER(IndexArrays), vp, vp]
+        L.tgsf_text_bam_submit.argtypes = [vp, vp, vp, u64, i, C.POINTER(IndexArrays), C.POINTER(BamSummary), C.POINTER(abi.BatchOut)]
+        L.tgsf_text_bam_filter.argtypes = [vp, vp, vp, u64, i, i, vp, u64, vp, C.POINTER(OutSummary), C.POINTER(BamSummary),
+                                           C.POINTER(IndexArrays), C.POINTER(abi.BatchOut)]
         if L.tgsf_text_abi_version() != ABI_VERSION:
             raise RuntimeError("libtgsf_text ABI version mismatch")
         _LIBS[path] = L
@@ -112,6 +136,30 @@ def _as_u8(text):
     if isinstance(text, (bytes, bytearray, memoryview)):
         return np.frombuffer(text, dtype=np.uint8)
     return np.ascontiguousarray(text, dtype=np.uint8)
+
+
+def bam_header(bam, lib_path: str | None = None) -> int:
+    """The offset of the first record's block_size in inflated BAM bytes that begin with the BAM header; TgsfError(-6) when
+    the magic is wrong or the header is not complete yet."""
+    L = load(lib_path)
+    b = _as_u8(bam)
+    at = C.c_uint64()
+    rc = L.tgsf_text_bam_header(b.ctypes.data, b.size, C.byref(at))
+    if rc != 0:
+        raise TgsfError(rc, L.tgsf_text_last_error(None).decode())
+    return at.value
+
+
+def bam_walk(bam, max_records: int, final=True, lib_path: str | None = None):
+    """The chain walk on the host: (rec_off of n + 1 entries as uint64, stop, consumed) for a chunk that begins at a record."""
+    L = load(lib_path)
+    b = _as_u8(bam)
+    rec_off = np.zeros(int(max_records) + 1, np.uint64)
+    n, stop, consumed = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    rc = L.tgsf_text_bam_walk(b.ctypes.data, b.size, int(final), int(max_records), rec_off.ctypes.data, C.byref(n), C.byref(stop), C.byref(consumed))
+    if rc != 0:
+        raise TgsfError(rc, L.tgsf_text_last_error(None).decode())
+    return rec_off[:n.value + 1].copy(), stop.value, consumed.value
 
 
 class TextIndexer:
@@ -270,6 +318,76 @@ class TextIndexer:
         rc = self.lib.tgsf_text_filter(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final), int(fastq_out), out.ctypes.data, cap,
                                        rec_end.ctypes.data, C.byref(so), C.byref(si), None, C.byref(bo) if bo is not None else None)
         self._chk_out(rc, so)
+        res = (out[:so.n_bytes].tobytes(), rec_end[:so.n_records].copy(), so.as_dict(), si.as_dict())
+        if want_results:
+            res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
+        return res
+
+    # ---- the BAM input side: inflated unaligned BAM records in -----------------------------------------------------------
+    def reserve_bam(self, max_bam_bytes):
+        """Once, before the first decode: the device buffer for chunks of up to max_bam_bytes and the per-record scratch."""
+        self._chk(self.lib.tgsf_text_bam_reserve(self.h, int(max_bam_bytes)))
+        self.max_bam_bytes = int(max_bam_bytes)
+
+    def bam_decode(self, bam, final=True, want_index=True):
+        """Decode a chunk of inflated BAM records held in host memory into the object's text buffer and index arrays:
+        (Index or None, summary dict).  The text itself stays on the device (buffers().text, summary["text_bytes"] bytes)."""
+        b = _as_u8(bam)
+        arrs, ia = self._host_index() if want_index else (None, None)
+        s = BamSummary()
+        self._chk(self.lib.tgsf_text_bam_decode(self.h, b.ctypes.data, b.size, int(final), C.byref(ia) if want_index else None, C.byref(s)))
+        return (self._clip(arrs, s.n_records) if want_index else None), s.as_dict()
+
+    def bam_decode_device(self, n_bytes, rec_off, walk_stop, final=True, d_bam=None, d_index: IndexArrays | None = None, d_summary=None, stream=None):
+        """Enqueue the decode of BAM bytes already in HBM (d_bam None: the object's buffer) without waiting; rec_off (uint64,
+        n_walked + 1 entries) and walk_stop are bam_walk()'s.  fetch() does not know this summary: read d_summary, or
+        buffers() after a synchronise."""
+        rec_off = np.ascontiguousarray(rec_off, dtype=np.uint64)
+        self._chk(self.lib.tgsf_text_bam_decode_device(self.h, d_bam, int(n_bytes), int(final), rec_off.ctypes.data, rec_off.size - 1, int(walk_stop),
+                                                       C.byref(d_index) if d_index is not None else None, d_summary, stream))
+
+    def _chk_bam(self, rc, s):
+        if rc != 0:
+            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            e.summary = s.as_dict()
+            raise e
+
+    def bam_submit(self, ctx, bam, final=True, frag_capacity=None, want_index=True):
+        """BAM in, filter results out: (Index or None, summary dict, reads, frags) for the indexed prefix of `bam`.  A quality
+        byte of 233 raises TgsfError(-6); its `summary` attribute holds bad_qual."""
+        b = _as_u8(bam)
+        if frag_capacity is None:
+            frag_capacity = b.size // 50 + self.max_records + 16
+        arrs, ia = self._host_index() if want_index else (None, None)
+        reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
+        frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
+        bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
+        s = BamSummary()
+        rc = self.lib.tgsf_text_bam_submit(self.h, ctx.h, b.ctypes.data, b.size, int(final), C.byref(ia) if want_index else None, C.byref(s), C.byref(bo))
+        self._chk_bam(rc, s)
+        n = s.n_records
+        return (self._clip(arrs, n) if want_index else None), s.as_dict(), reads[:n].copy(), frags[:bo.n_frags].copy()
+
+    def bam_filter(self, ctx, bam, final=True, fastq_out=True, out=None, out_capacity=None, frag_capacity=None, want_results=False):
+        """BAM in, clean text out: (the text as bytes, rec_end, out summary dict, BAM summary dict) for the indexed prefix of
+        `bam`; with want_results also the per-read records and the fragments, as bam_submit() returns them."""
+        b = _as_u8(bam)
+        out, cap = self._out(out, out_capacity)
+        rec_end = np.zeros(max(getattr(self, "max_frags", 0), 1), np.uint64)
+        so, si = OutSummary(), BamSummary()
+        bo = reads = frags = None
+        if want_results:
+            if frag_capacity is None:
+                frag_capacity = b.size // 50 + self.max_records + 16
+            reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
+            frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
+            bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
+        rc = self.lib.tgsf_text_bam_filter(self.h, ctx.h, b.ctypes.data, b.size, int(final), int(fastq_out), out.ctypes.data, cap,
+                                           rec_end.ctypes.data, C.byref(so), C.byref(si), None, C.byref(bo) if bo is not None else None)
+        if rc != 0:
+            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            e.summary, e.in_summary = so.as_dict(), si.as_dict()
+            raise e
         res = (out[:so.n_bytes].tobytes(), rec_end[:so.n_records].copy(), so.as_dict(), si.as_dict())
         if want_results:
             res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
