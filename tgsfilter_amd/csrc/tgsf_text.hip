@@ -161,14 +161,14 @@ static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int f
     if (tx->profile) (void)rt_event_record(tx->ev[0], st);
     if (pieces) {
         TGSF_LAUNCH(k_text_mark, gwave, kTextThreads, st, d_text, n, pieces, (uint16_t*)tx->d_bits, tx->d_cnt);
-        TGSF_LAUNCH_COOP(k_text_scan_tiles, nb, 256, st, tx->d_cnt, pieces, tx->d_part);
+        TGSF_LAUNCH_COOP(k_text_scan_tiles<uint32_t>, nb, 256, st, tx->d_cnt, pieces, tx->d_part);
     }
     TGSF_LAUNCH_COOP(k_text_scan_top, 1, 64, st, tx->d_part, nb, tx->d_state);
     if (pieces)
         TGSF_LAUNCH(k_text_emit, gemit, kTextThreads, st, (const uint64_t*)tx->d_bits, (const uint32_t*)tx->d_cnt,
                     (const uint64_t*)tx->d_part, pieces, tx->d_table, cap);
     TGSF_LAUNCH(k_text_check, gsmall, kTextThreads, st, d_text, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, tx->d_state, I);
-    TGSF_LAUNCH(k_text_fold, gfold, kTextThreads, st, (const uint32_t*)I.len, fasta, tx->max_records, tx->d_state);
+    TGSF_LAUNCH(k_text_fold<TextState>, gfold, kTextThreads, st, (const uint32_t*)I.len, tx->max_records, fasta, tx->d_state);
     TGSF_LAUNCH_COOP(k_text_finish, 1, 64, st, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, (const TextState*)tx->d_state, d_summary);
     if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
     if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
@@ -234,6 +234,20 @@ extern "C" int tgsf_text_index_device(tgsf_text* tx, const uint8_t* d_text, uint
                          hip_stream ? (rt_stream)hip_stream : tx->stream);
 }
 
+// the first k entries of the object's own index to the host, on the object's stream, which is waited for
+static int fetch_index(tgsf_text* tx, const tgsf_text_index_arrays* out_index, size_t k)
+{
+    if (!out_index || !k) return TGSF_OK;
+    int he = 0;
+    if (out_index->seq_off) he |= rt_d2h(out_index->seq_off, tx->d_index.seq_off, k * 8, tx->stream);
+    if (out_index->qual_off) he |= rt_d2h(out_index->qual_off, tx->d_index.qual_off, k * 8, tx->stream);
+    if (out_index->len) he |= rt_d2h(out_index->len, tx->d_index.len, k * 4, tx->stream);
+    if (out_index->name_off) he |= rt_d2h(out_index->name_off, tx->d_index.name_off, k * 8, tx->stream);
+    if (out_index->name_len) he |= rt_d2h(out_index->name_len, tx->d_index.name_len, k * 4, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    return he ? fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he)) : TGSF_OK;
+}
+
 // the object's own summary and index to the host; the copies run on the object's stream, which is waited for
 static int fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_text_summary* sum)
 {
@@ -241,16 +255,8 @@ static int fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_te
     if (!he) he = rt_sync(tx->stream);
     if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
     sum->device_ms = index_ms(tx);
-    const size_t k = sum->n_records;
-    if (out_index && k) {
-        if (out_index->seq_off) he |= rt_d2h(out_index->seq_off, tx->d_index.seq_off, k * 8, tx->stream);
-        if (out_index->qual_off) he |= rt_d2h(out_index->qual_off, tx->d_index.qual_off, k * 8, tx->stream);
-        if (out_index->len) he |= rt_d2h(out_index->len, tx->d_index.len, k * 4, tx->stream);
-        if (out_index->name_off) he |= rt_d2h(out_index->name_off, tx->d_index.name_off, k * 8, tx->stream);
-        if (out_index->name_len) he |= rt_d2h(out_index->name_len, tx->d_index.name_len, k * 4, tx->stream);
-        if (!he) he = rt_sync(tx->stream);
-        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    }
+    const int e = fetch_index(tx, out_index, sum->n_records);
+    if (e) return e;
     if (out_summary) *out_summary = *sum;
     return TGSF_OK;
 }
@@ -278,12 +284,12 @@ extern "C" int tgsf_text_index(tgsf_text* tx, const uint8_t* text, uint64_t n_by
 }
 
 // The filter on the text and the index that are in the object (n_records of them, n_bytes of text), through ctx; bo == NULL:
-// nothing comes down.  The fragments go to d_fr on the device (room for fr_cap; NULL: not wanted), their number to *n_frags.
+// nothing comes down.  The fragments go to d_fr on the device (room for fr_cap; NULL: not wanted), their number to *n_frags
+// (and to bo->n_frags, which the caller has zeroed).
 static int run_filter(tgsf_text* tx, tgsf_ctx* ctx, uint32_t n_records, uint64_t n_bytes, tgsf_batch_out* bo, tgsf_fragment* d_fr,
                       uint32_t fr_cap, uint32_t* n_frags)
 {
     int e;
-    if (bo) bo->n_frags = 0;
     *n_frags = 0;
     if (n_records) {
         tgsf_batch_in in;
@@ -319,26 +325,6 @@ static int run_filter(tgsf_text* tx, tgsf_ctx* ctx, uint32_t n_records, uint64_t
     return TGSF_OK;
 }
 
-// tgsf_text_submit; bo == NULL (tgsf_text_filter only): nothing but the summary comes down.  The fragments go to d_fr on the
-// device (room for fr_cap; NULL: not wanted), their number to *n_frags.
-static int submit_core(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
-                       const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo,
-                       tgsf_fragment* d_fr, uint32_t fr_cap, uint32_t* n_frags)
-{
-    int e;
-    if ((e = upload(tx, text, n_bytes))) return e;
-    if ((e = enqueue_index(tx, tx->d_text, n_bytes, fasta, final, tx->d_index, tx->d_summary, tx->stream))) return e;
-    tgsf_text_summary sum;
-    // the one wait between the index and the filter: libtgsf sizes its launches by n_reads on the host
-    if ((e = fetch(tx, nullptr, nullptr, &sum))) return e;
-    if ((e = run_filter(tx, ctx, sum.n_records, n_bytes, bo, d_fr, fr_cap, n_frags))) return e;
-    // the index last: the filter does not wait for it
-    tgsf_text_summary again;
-    if (out_index && (e = fetch(tx, out_index, nullptr, &again))) return e;
-    *out_summary = sum;
-    return TGSF_OK;
-}
-
 // fragment records on the device for a caller who takes them: as many as the caller takes
 static int grow_frags(tgsf_text* tx, const tgsf_batch_out* bo)
 {
@@ -349,20 +335,6 @@ static int grow_frags(tgsf_text* tx, const tgsf_batch_out* bo)
         tx->frag_cap = bo->frag_capacity;
     }
     return TGSF_OK;
-}
-
-extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
-                                const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo)
-{
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_args(tx, n_bytes, fasta, final);
-    if (e) return e;
-    (void)rt_set_device(tx->device);
-    if ((e = grow_frags(tx, bo))) return e;
-    uint32_t nf = 0;
-    return submit_core(tx, ctx, text, n_bytes, fasta, final, out_index, out_summary, bo, bo->frags ? tx->d_frags : nullptr,
-                       bo->frags ? bo->frag_capacity : 0u, &nf);
 }
 
 // ---- the output side ---------------------------------------------------------------------------------------------------
@@ -416,13 +388,13 @@ static int enqueue_format(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_
     TextOutState* S = tx->d_ostate;
     if (tx->profile) (void)rt_event_record(tx->oev[0], st);
     TGSF_LAUNCH(k_textout_flag, gfrag, kTextThreads, st, d_frags, n, tx->d_opass, S);
-    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles, nb, 256, st, tx->d_opass, n, tx->d_opass_part);
+    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles<uint32_t>, nb, 256, st, tx->d_opass, n, tx->d_opass_part);
     TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_opass_part, nb, &S->n_records);
     if (n)
         TGSF_LAUNCH(k_textout_size, gfrag, kTextThreads, st, d_text, I, d_reads, d_frags, n, fastq_out, (const uint32_t*)tx->d_opass,
                     (const uint64_t*)tx->d_opass_part, tx->d_osize, tx->d_ometa, S);
     if (tx->profile) (void)rt_event_record(tx->oev[1], st);
-    if (n) TGSF_LAUNCH_COOP(k_textout_scan_tiles64, nb, 256, st, tx->d_osize, n, tx->d_osize_part);
+    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_osize, n, tx->d_osize_part);
     TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_osize_part, nb, &S->n_bytes);
     TGSF_LAUNCH(k_textout_finish, gfrag, kTextThreads, st, (const uint64_t*)tx->d_osize, (const uint64_t*)tx->d_osize_part,
                 (const uint32_t*)tx->d_opass, (const uint64_t*)tx->d_opass_part, (const TextOutMeta*)tx->d_ometa, n, capacity,
@@ -524,28 +496,6 @@ extern "C" int tgsf_text_format(tgsf_text* tx, uint32_t n_records, int fasta, co
     return format_down(tx, tx->d_reads, tx->d_ofrags, n_frags, fastq_out, out, out_capacity, rec_end, out_summary);
 }
 
-extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
-                                uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
-                                tgsf_text_summary* in_summary,
-                                const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
-{
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!text && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, fasta, fastq_out);
-    if (!e) e = check_args(tx, n_bytes, fasta, final);
-    if (e) return e;
-    (void)rt_set_device(tx->device);
-    const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts, as in tgsf_text_submit
-    if (down && (e = grow_frags(tx, bo))) return e;
-    tgsf_fragment* d_fr = down ? tx->d_frags : tx->d_ofrags;
-    uint32_t nf = 0;
-    memset(out_summary, 0, sizeof *out_summary);
-    if ((e = submit_core(tx, ctx, text, n_bytes, fasta, final, out_index, in_summary, bo, d_fr, down ? bo->frag_capacity : tx->max_frags, &nf))) return e;
-    if (!in_summary->n_records) return TGSF_OK;                        // nothing ran: an empty output, no error
-    if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
-    return format_down(tx, tx->d_reads, d_fr, nf, fastq_out, out, out_capacity, rec_end, out_summary);
-}
-
 // ---- the BAM input side --------------------------------------------------------------------------------------------------
 extern "C" int tgsf_text_bam_header(const uint8_t* bam, uint64_t n_bytes, uint64_t* records_at)
 {
@@ -644,11 +594,11 @@ static int enqueue_bam(tgsf_text* tx, const uint8_t* d_bam, const uint64_t* rec_
     TGSF_LAUNCH_COOP(k_bam_reset, 1, 64, st, S);
     if (n) {
         TGSF_LAUNCH(k_bam_heads, grec, kTextThreads, st, d_bam, (const uint64_t*)tx->d_brec_off, n_walked, tx->d_bsize, tx->d_boseq, I, S);
-        TGSF_LAUNCH_COOP(k_textout_scan_tiles64, nb, 256, st, tx->d_bsize, n, tx->d_bsize_part);
+        TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_bsize, n, tx->d_bsize_part);
         TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_bsize_part, nb, &S->total);
         TGSF_LAUNCH(k_bam_layout, grec, kTextThreads, st, (const uint64_t*)tx->d_bsize, (const uint64_t*)tx->d_bsize_part, n_walked, tx->max_bytes, S,
                     tx->d_bends, I);
-        TGSF_LAUNCH(k_bam_fold, gfold, kTextThreads, st, (const uint32_t*)I.len, n_walked, S);
+        TGSF_LAUNCH(k_text_fold<BamState>, gfold, kTextThreads, st, (const uint32_t*)I.len, n_walked, 0, S);
     }
     TGSF_LAUNCH_COOP(k_bam_finish, 1, 64, st, (const uint64_t*)tx->d_brec_off, (const uint64_t*)tx->d_bends, n_walked, walk_stop, (const BamState*)S, d_summary);
     TGSF_LAUNCH(k_bam_unpack, gtext, kTextThreads, st, d_bam, (const uint64_t*)tx->d_brec_off, (const uint32_t*)tx->d_boseq, I,
@@ -692,19 +642,6 @@ static int bam_decode_down(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, 
     return TGSF_OK;
 }
 
-static int fetch_index(tgsf_text* tx, const tgsf_text_index_arrays* out_index, size_t k)
-{
-    if (!out_index || !k) return TGSF_OK;
-    int he = 0;
-    if (out_index->seq_off) he |= rt_d2h(out_index->seq_off, tx->d_index.seq_off, k * 8, tx->stream);
-    if (out_index->qual_off) he |= rt_d2h(out_index->qual_off, tx->d_index.qual_off, k * 8, tx->stream);
-    if (out_index->len) he |= rt_d2h(out_index->len, tx->d_index.len, k * 4, tx->stream);
-    if (out_index->name_off) he |= rt_d2h(out_index->name_off, tx->d_index.name_off, k * 8, tx->stream);
-    if (out_index->name_len) he |= rt_d2h(out_index->name_len, tx->d_index.name_len, k * 4, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    return he ? fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he)) : TGSF_OK;
-}
-
 extern "C" int tgsf_text_bam_decode(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, const tgsf_text_index_arrays* out_index,
                                     tgsf_text_bam_summary* out_summary)
 {
@@ -728,23 +665,92 @@ static int bad_quality(tgsf_text* tx, const uint8_t* bam, const tgsf_text_bam_su
     return fail(tx, TGSF_E_DATA, "unsupported quality value in %.*s (record %u of the chunk): the filter has not run", (int)strnlen(name, r[8]), name, sum.bad_qual);
 }
 
+// ---- the one path of the four calls that run the filter: ingest, filter, format ------------------------------------------------
+// How the chunk gets into the object and where its summary goes.  Text (text_summary): upload and index; the caller's summary
+// is written when the call has succeeded.  BAM (bam_summary): walk, copy up, decode; the text has text_bytes bytes, the
+// caller's summary is written before the filter runs, and a quality that decodes to '\n' refuses the chunk.
+struct Ingest {
+    const uint8_t* bytes;
+    uint64_t n_bytes;
+    int fasta, final;
+    tgsf_text_summary* text_summary;
+    tgsf_text_bam_summary* bam_summary;
+};
+// where tgsf_text_filter and tgsf_text_bam_filter have the kept records formatted to
+struct FormatTo {
+    int fastq_out;
+    uint8_t* out;
+    uint64_t out_capacity;
+    uint64_t* rec_end;
+    tgsf_text_out_summary* out_summary;
+};
+
+// The chunk into the object, the one wait for the record count (libtgsf sizes its launches by n_reads on the host), the filter,
+// the index down last (the filter does not wait for it); with `to` the kept records as text.  The arguments have been checked.
+static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo,
+                                const FormatTo* to)
+{
+    int e;
+    (void)rt_set_device(tx->device);
+    const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts
+    if (down && (e = grow_frags(tx, bo))) return e;
+    tgsf_fragment* d_fr = down ? tx->d_frags : (to ? tx->d_ofrags : nullptr);
+    const uint32_t fr_cap = down ? bo->frag_capacity : (to ? tx->max_frags : 0u);
+    if (to) memset(to->out_summary, 0, sizeof *to->out_summary);
+    tgsf_text_summary ts;
+    tgsf_text_bam_summary bs;
+    if (in.bam_summary) {
+        if ((e = bam_decode_down(tx, in.bytes, in.n_bytes, in.final, &bs))) return e;
+        *in.bam_summary = bs;
+    } else {
+        if ((e = upload(tx, in.bytes, in.n_bytes))) return e;
+        if ((e = enqueue_index(tx, tx->d_text, in.n_bytes, in.fasta, in.final, tx->d_index, tx->d_summary, tx->stream))) return e;
+        if ((e = fetch(tx, nullptr, nullptr, &ts))) return e;
+    }
+    const uint32_t n_records = in.bam_summary ? bs.n_records : ts.n_records;
+    if (bo) bo->n_frags = 0;
+    if (in.bam_summary && bs.bad_qual != 0xFFFFFFFFu) return bad_quality(tx, in.bytes, bs);
+    uint32_t nf = 0;
+    if ((e = run_filter(tx, ctx, n_records, in.bam_summary ? bs.text_bytes : in.n_bytes, bo, d_fr, fr_cap, &nf))) return e;
+    if ((e = fetch_index(tx, out_index, n_records))) return e;
+    if (in.text_summary) *in.text_summary = ts;
+    if (!to || !n_records) return TGSF_OK;                             // no record: nothing ran, an empty output, no error
+    if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
+    return format_down(tx, tx->d_reads, d_fr, nf, to->fastq_out, to->out, to->out_capacity, to->rec_end, to->out_summary);
+}
+
+extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
+                                const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    const int e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+    return ingest_filter_format(tx, ctx, {text, n_bytes, fasta, final, out_summary, nullptr}, out_index, bo, nullptr);
+}
+
+extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
+                                uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                                tgsf_text_summary* in_summary,
+                                const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!text && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, fasta, fastq_out);
+    if (!e) e = check_args(tx, n_bytes, fasta, final);
+    if (e) return e;
+    const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
+    return ingest_filter_format(tx, ctx, {text, n_bytes, fasta, final, in_summary, nullptr}, out_index, bo, &to);
+}
+
 extern "C" int tgsf_text_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final,
                                     const tgsf_text_index_arrays* out_index, tgsf_text_bam_summary* out_summary, tgsf_batch_out* bo)
 {
     if (!tx) return TGSF_E_INVALID;
     if (!ctx || !out_summary || !bo || !bo->reads || (!bam && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_bam(tx, n_bytes, final);
+    const int e = check_bam(tx, n_bytes, final);
     if (e) return e;
-    (void)rt_set_device(tx->device);
-    if ((e = grow_frags(tx, bo))) return e;
-    tgsf_text_bam_summary sum;
-    if ((e = bam_decode_down(tx, bam, n_bytes, final, &sum))) return e;
-    *out_summary = sum;
-    bo->n_frags = 0;
-    if (sum.bad_qual != 0xFFFFFFFFu) return bad_quality(tx, bam, sum);
-    uint32_t nf = 0;
-    if ((e = run_filter(tx, ctx, sum.n_records, sum.text_bytes, bo, bo->frags ? tx->d_frags : nullptr, bo->frags ? bo->frag_capacity : 0u, &nf))) return e;
-    return fetch_index(tx, out_index, sum.n_records);                  // the index last: the filter does not wait for it
+    return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, out_summary}, out_index, bo, nullptr);
 }
 
 extern "C" int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
@@ -756,20 +762,6 @@ extern "C" int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t*
     int e = check_format(tx, 0, 0, fastq_out);
     if (!e) e = check_bam(tx, n_bytes, final);
     if (e) return e;
-    (void)rt_set_device(tx->device);
-    const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts, as in tgsf_text_bam_submit
-    if (down && (e = grow_frags(tx, bo))) return e;
-    tgsf_fragment* d_fr = down ? tx->d_frags : tx->d_ofrags;
-    memset(out_summary, 0, sizeof *out_summary);
-    tgsf_text_bam_summary sum;
-    if ((e = bam_decode_down(tx, bam, n_bytes, final, &sum))) return e;
-    *in_summary = sum;
-    if (bo) bo->n_frags = 0;
-    if (sum.bad_qual != 0xFFFFFFFFu) return bad_quality(tx, bam, sum);
-    uint32_t nf = 0;
-    if ((e = run_filter(tx, ctx, sum.n_records, sum.text_bytes, bo, d_fr, down ? bo->frag_capacity : tx->max_frags, &nf))) return e;
-    if ((e = fetch_index(tx, out_index, sum.n_records))) return e;
-    if (!sum.n_records) return TGSF_OK;                                // nothing ran: an empty output, no error
-    if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
-    return format_down(tx, tx->d_reads, d_fr, nf, fastq_out, out, out_capacity, rec_end, out_summary);
+    const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
+    return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
 }

@@ -2,13 +2,15 @@
 //
 //   k_text_mark        one streaming read of the text, 16 bytes a lane: a bit per byte ('\n' or not) and the number of
 //                      line ends of every 4 KiB piece (one wave's share).  The text is not read again as a stream.
-//   k_text_scan_tiles  } exclusive prefix sums of those counts: the scheme of k_scan_tiles / k_scan_top in tgsf_kernels.h
-//   k_text_scan_top    } (restated here; the offset of a block of counts is added by the reader, not by a third launch)
+//   k_text_scan_tiles  } exclusive prefix sums of those counts: the scheme of k_scan_tiles / k_scan_top in tgsf_kernels.h,
+//   k_text_scan_top    } restated here once for every scan of this library (k_text_scan_tiles<uint32_t> and <uint64_t>,
+//                        text_scan_top); the offset of a block of counts is added by the reader, not by a third launch
 //   k_text_emit        every wave turns the bits of four pieces into 64-bit positions, in order, at each piece's offset of
 //                      the line-end table (lane prefix count, no atomics); only the first 4 * max_records are kept
 //   k_text_check       a lane per group of 4 (2) lines: five table entries, the first byte of lines 0 and 2, the byte in
 //                      front of each line end ('\r'); writes the record's index words, folds the first irregular group
-//   k_text_fold        bases and longest over the regular prefix (per wave first, then one atomic)
+//   k_text_fold        bases and longest over the records of the index (per wave first, then one atomic); k_text_fold<TextState>
+//                      here, k_text_fold<BamState> on the BAM input side
 //   k_text_finish      one lane: n_records, consumed, why the index ends
 //
 // Compiled by hipcc for gfx950 and, with -DTGSF_EMUL, by g++ for the serial emulation of tests/emul, in which every lane
@@ -49,6 +51,12 @@ constexpr uint32_t kTextLanes = 1;
 TGSF_HD uint32_t wave_excl_scan(uint32_t) { return 0; }
 TGSF_HD uint32_t wave_min(uint32_t v) { return v; }
 #endif
+// the lowest v of the wave into *lowest, by one atomic of its leader (0xFFFFFFFF in every lane: none)
+TGSF_D void wave_min_into(uint32_t* lowest, uint32_t v)
+{
+    v = wave_min(v);
+    if (wave_leader() && v != 0xFFFFFFFFu) atomicMin(lowest, v);
+}
 
 constexpr uint32_t kTextThreads = 256;                    // lanes of a workgroup of the wave-per-piece kernels
 constexpr uint32_t kTextPiece = 4096;                     // bytes of text a wave marks / emits: 4 loads of 16 bytes a lane
@@ -107,34 +115,41 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_text_mark(const uint8_t* __restrict__
 }
 
 // a[0..n) -> exclusive prefix sums within blocks of kTextScanTile entries, in place; part[b] = the block's total
-TGSF_KERNEL k_text_scan_tiles(uint32_t* a, uint64_t n, uint64_t* part)
+template <typename T> TGSF_KERNEL k_text_scan_tiles(T* a, uint64_t n, uint64_t* part)
 {
-    TGSF_SHARED uint32_t sums[1024];
-    const uint32_t T = blockDim.x, per = (kTextScanTile + T - 1) / T;
+    TGSF_SHARED T sums[1024];
+    const uint32_t B = blockDim.x, per = (kTextScanTile + B - 1) / B;
     const uint64_t base = blockIdx.x * (uint64_t)kTextScanTile;
     const uint64_t lo = base + threadIdx.x * per;
     uint64_t hi = lo + per;
     if (hi > base + kTextScanTile) hi = base + kTextScanTile;
     if (hi > n) hi = n;
-    uint32_t s = 0;
+    T s = 0;
     for (uint64_t i = lo; i < hi; i++) s += a[i];
     sums[threadIdx.x] = s;
     TGSF_BLOCK_SYNC();
     if (threadIdx.x == 0) {
-        uint32_t acc = 0;
-        for (uint32_t t = 0; t < T; t++) { const uint32_t x = sums[t]; sums[t] = acc; acc += x; }
+        T acc = 0;
+        for (uint32_t t = 0; t < B; t++) { const T x = sums[t]; sums[t] = acc; acc += x; }
         part[blockIdx.x] = acc;
     }
     TGSF_BLOCK_SYNC();
-    uint32_t acc = sums[threadIdx.x];
-    for (uint64_t i = lo; i < hi; i++) { const uint32_t x = a[i]; a[i] = acc; acc += x; }
+    T acc = sums[threadIdx.x];
+    for (uint64_t i = lo; i < hi; i++) { const T x = a[i]; a[i] = acc; acc += x; }
 }
-// part[0..nb) -> exclusive prefix sums (64-bit: a chunk of newlines only has more than 2^32 of them); resets the state
+// part[0..nb) -> exclusive prefix sums, by the one lane that calls it; returns the total (nb == 0: 0).  64-bit: a chunk of
+// newlines only has more than 2^32 of them
+TGSF_D uint64_t text_scan_top(uint64_t* part, uint32_t nb)
+{
+    uint64_t acc = 0;
+    for (uint32_t b = 0; b < nb; b++) { const uint64_t x = part[b]; part[b] = acc; acc += x; }
+    return acc;
+}
+// ... of the line ends; resets the state
 TGSF_KERNEL k_text_scan_top(uint64_t* part, uint32_t nb, TextState* S)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint64_t acc = 0;
-    for (uint32_t b = 0; b < nb; b++) { const uint64_t x = part[b]; part[b] = acc; acc += x; }
+    const uint64_t acc = text_scan_top(part, nb);
     S->total = acc; S->lines = acc; S->bases = 0; S->first_bad = 0xFFFFFFFFu; S->longest = 0;
 }
 
@@ -214,19 +229,21 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_text_check(const uint8_t* __restrict_
             I.name_len[g] = (uint32_t)(len[0] - 1);
         } else if ((uint32_t)g < bad) bad = (uint32_t)g;
     }
-    bad = wave_min(bad);
-    if (wave_leader() && bad != 0xFFFFFFFFu) atomicMin(&S->first_bad, bad);
+    wave_min_into(&S->first_bad, bad);
 }
 
-TGSF_D uint32_t text_records(const TextState* S, uint32_t G, uint32_t max_records)
+// records of the index: the regular groups of G lines in front of the first that is not, max_records at most
+TGSF_D uint32_t index_records(const TextState* S, uint32_t max_records, uint32_t G)
 {
     const uint64_t groups = S->lines / G < max_records ? S->lines / G : max_records;
     return S->first_bad < groups ? S->first_bad : (uint32_t)groups;
 }
 
-TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_text_fold(const uint32_t* __restrict__ len, int fasta, uint32_t max_records, TextState* S)
+// State: TextState (limit: max_records; fasta: 2 lines a record, not 4) or BamState (limit: n_walked); its index_records() counts
+template <typename State>
+TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_text_fold(const uint32_t* __restrict__ len, uint32_t limit, int fasta, State* S)
 {
-    const uint32_t nrec = text_records(S, fasta ? 2u : 4u, max_records);
+    const uint32_t nrec = index_records(S, limit, fasta ? 2u : 4u);
     const uint64_t gid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, stride = gridDim.x * (uint64_t)blockDim.x;
     uint64_t sum = 0;
     uint32_t mx = 0;
@@ -245,7 +262,7 @@ TGSF_KERNEL k_text_finish(uint64_t n, int fasta, int final, const uint64_t* tabl
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const uint32_t G = fasta ? 2u : 4u;
     const uint64_t groups = S->lines / G < max_records ? S->lines / G : max_records;
-    const uint32_t k = text_records(S, G, max_records);
+    const uint32_t k = index_records(S, max_records, G);
     const uint64_t last = (uint64_t)G * k;                             // lines of the index
     const uint64_t left = S->lines - last;
     uint32_t stop;
@@ -264,10 +281,10 @@ TGSF_KERNEL k_text_finish(uint64_t n, int fasta, int final, const uint64_t* tabl
 // ---- the output side: the kept records as clean FASTQ / FASTA text (tgsf_text_format*) -------------------------------
 //
 //   k_textout_flag     a lane per fragment: 1 for TGSF_FF_PASS, else 0
-//   (k_text_scan_tiles / k_textout_scan_top: exclusive prefix sums of the flags -- a fragment's pass_num is its sum minus
+//   (k_text_scan_tiles<uint32_t> / k_textout_scan_top: exclusive prefix sums of the flags -- a fragment's pass_num is its sum minus
 //    the sum at its read's frag_begin, plus one; a read may have thousands of fragments, nobody walks them)
 //   k_textout_size     a lane per fragment: the record's size (0 without PASS), for pass_num >= 2 where ":<n>" goes into the name
-//   (k_textout_scan_tiles64 / k_textout_scan_top: exclusive prefix sums of the sizes, 64-bit)
+//   (k_text_scan_tiles<uint64_t> / k_textout_scan_top: exclusive prefix sums of the sizes, 64-bit)
 //   k_textout_finish   a lane per fragment: the byte behind each record (ends[]; the caller's rec_end), the summary; decides CAPACITY
 //   k_textout_copy     the hot path: waves stride over 4 KiB pieces of the OUTPUT; a lane owns aligned 16-byte chunks.  A chunk
 //                      inside one sequence or quality stretch is one load16u and one store; a chunk that touches a seam is put
@@ -315,36 +332,11 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_textout_flag(const tgsf_fragment* __r
     for (uint64_t f = gid; f < n_frags; f += stride) pass[f] = frags[f].flags & TGSF_FF_PASS ? 1u : 0u;
 }
 
-// a[0..n) -> exclusive prefix sums within blocks of kTextScanTile entries, in place; part[b] = the block's total (k_text_scan_tiles, 64-bit)
-TGSF_KERNEL k_textout_scan_tiles64(uint64_t* a, uint64_t n, uint64_t* part)
-{
-    TGSF_SHARED uint64_t sums[1024];
-    const uint32_t T = blockDim.x, per = (kTextScanTile + T - 1) / T;
-    const uint64_t base = blockIdx.x * (uint64_t)kTextScanTile;
-    const uint64_t lo = base + threadIdx.x * per;
-    uint64_t hi = lo + per;
-    if (hi > base + kTextScanTile) hi = base + kTextScanTile;
-    if (hi > n) hi = n;
-    uint64_t s = 0;
-    for (uint64_t i = lo; i < hi; i++) s += a[i];
-    sums[threadIdx.x] = s;
-    TGSF_BLOCK_SYNC();
-    if (threadIdx.x == 0) {
-        uint64_t acc = 0;
-        for (uint32_t t = 0; t < T; t++) { const uint64_t x = sums[t]; sums[t] = acc; acc += x; }
-        part[blockIdx.x] = acc;
-    }
-    TGSF_BLOCK_SYNC();
-    uint64_t acc = sums[threadIdx.x];
-    for (uint64_t i = lo; i < hi; i++) { const uint64_t x = a[i]; a[i] = acc; acc += x; }
-}
 // part[0..nb) -> exclusive prefix sums; the total (nb == 0: 0)
 TGSF_KERNEL k_textout_scan_top(uint64_t* part, uint32_t nb, uint64_t* total)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    uint64_t acc = 0;
-    for (uint32_t b = 0; b < nb; b++) { const uint64_t x = part[b]; part[b] = acc; acc += x; }
-    *total = acc;
+    *total = text_scan_top(part, nb);
 }
 
 TGSF_HD bool textout_isspace(uint8_t c) { return c == ' ' || (c >= '\t' && c <= '\r'); }    // " \t\n\v\f\r" (newSeqName)
@@ -531,10 +523,10 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_textout_copy(const uint8_t* __restric
 //   k_bam_reset        one lane: the state
 //   k_bam_heads        a lane per walked record: its fields by byte loads (record starts have no alignment), regular or not,
 //                      name_len (strnlen), l_seq, where the packed bases begin, the size of its piece of text (0: not regular)
-//   (k_textout_scan_tiles64 / k_textout_scan_top: exclusive prefix sums of the sizes)
+//   (k_text_scan_tiles<uint64_t> / k_textout_scan_top: exclusive prefix sums of the sizes)
 //   k_bam_layout       a lane per walked record: the byte behind its text (ends[]), its index words, the first one that ends
 //                      behind max_bytes
-//   k_bam_fold         bases and longest over the prefix that is indexed
+//   (k_text_fold<BamState>: bases and longest over the prefix that is indexed)
 //   k_bam_finish       one lane: the summary
 //   k_bam_unpack       the hot path, driven by the OUTPUT as k_textout_copy is: waves stride over 4 KiB pieces of the text, a
 //                      lane owns aligned 16-byte chunks.  A chunk inside a base stretch is 8 packed bytes (9 when it starts on
@@ -553,7 +545,7 @@ struct BamState {
 TGSF_HD uint32_t bam_le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
 TGSF_HD uint32_t bam_le32(const uint8_t* p) { return bam_le16(p) | bam_le16(p + 2) << 16; }
 // records of the index: the walked ones in front of the first that is not regular and the first that does not fit
-TGSF_D uint32_t bam_records(const BamState* S, uint32_t n_walked)
+TGSF_D uint32_t index_records(const BamState* S, uint32_t n_walked, uint32_t = 0)
 {
     const uint32_t k = S->first_bad < S->first_over ? S->first_bad : S->first_over;
     return k < n_walked ? k : n_walked;
@@ -588,8 +580,7 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bam_heads(const uint8_t* __restrict__
         I.len[i] = l_seq;
         if (!ok && (uint32_t)i < bad) bad = (uint32_t)i;
     }
-    bad = wave_min(bad);
-    if (wave_leader() && bad != 0xFFFFFFFFu) atomicMin(&S->first_bad, bad);
+    wave_min_into(&S->first_bad, bad);
 }
 
 TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bam_layout(const uint64_t* __restrict__ size_excl, const uint64_t* __restrict__ size_part,
@@ -609,30 +600,14 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bam_layout(const uint64_t* __restrict
         I.qual_off[i] = seq + I.len[i] + 3u;
         if (end > max_bytes && (uint32_t)i < over) over = (uint32_t)i;
     }
-    over = wave_min(over);
-    if (wave_leader() && over != 0xFFFFFFFFu) atomicMin(&S->first_over, over);
-}
-
-TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bam_fold(const uint32_t* __restrict__ len, uint32_t n_walked, BamState* S)
-{
-    const uint32_t nrec = bam_records(S, n_walked);
-    const uint64_t gid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x, stride = gridDim.x * (uint64_t)blockDim.x;
-    uint64_t sum = 0;
-    uint32_t mx = 0;
-    for (uint64_t g = gid; g < nrec; g += stride) { const uint32_t l = len[g]; sum += l; mx = l > mx ? l : mx; }
-    sum = wave_sum(sum);
-    mx = wave_max(mx);
-    if (wave_leader() && mx) {
-        atomicAdd((text_ull*)&S->bases, (text_ull)sum);
-        atomicMax(&S->longest, mx);
-    }
+    wave_min_into(&S->first_over, over);
 }
 
 TGSF_KERNEL k_bam_finish(const uint64_t* rec_off, const uint64_t* ends, uint32_t n_walked, uint32_t walk_stop, const BamState* S,
                          tgsf_text_bam_summary* out)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const uint32_t k = bam_records(S, n_walked);
+    const uint32_t k = index_records(S, n_walked);
     out->n_records = k;
     out->stop = k == n_walked ? walk_stop : (S->first_bad == k ? (uint32_t)TGSF_TEXT_IRREGULAR : (uint32_t)TGSF_TEXT_CAPACITY);
     out->consumed = rec_off[k];                                        // (n_walked + 1 entries)
@@ -794,8 +769,7 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bam_unpack(const uint8_t* __restrict_
                 for (uint32_t i = 0; i < nb; i++) text[o + i] = (uint8_t)((i < 8 ? lo >> (8u * i) : hi >> (8u * (i - 8u))) & 0xFFu);
         }
     }
-    bad = wave_min(bad);
-    if (wave_leader() && bad != 0xFFFFFFFFu) atomicMin(&sum->bad_qual, bad);
+    wave_min_into(&sum->bad_qual, bad);
 }
 
 }  // namespace tgsf

@@ -174,9 +174,15 @@ class TextIndexer:
             raise TgsfError(rc, self.lib.tgsf_text_last_error(None).decode())
         self.h = h
 
-    def _chk(self, rc):
+    def _chk(self, rc, summary=None, in_summary=None):
+        """Raise what a call refused; the summaries it filled go along as the attributes `summary` and `in_summary`."""
         if rc != 0:
-            raise TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            if summary is not None:
+                e.summary = summary.as_dict()
+            if in_summary is not None:
+                e.in_summary = in_summary.as_dict()
+            raise e
 
     def close(self):
         if getattr(self, "h", None):
@@ -237,21 +243,29 @@ class TextIndexer:
         self._chk(self.lib.tgsf_text_fetch(self.h, C.byref(ia), C.byref(s)))
         return self._clip(arrs, s.n_records), s.as_dict()
 
+    def _results(self, frag_capacity, expected_frags):
+        """Host tables for the filter's results and the tgsf_batch_out over them; frag_capacity None: room for the fragments
+        expected of the chunk's size, one more per record, and 16."""
+        if frag_capacity is None:
+            frag_capacity = expected_frags + self.max_records + 16
+        reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
+        frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
+        return reads, frags, abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
+
+    def _submit(self, call, s, frag_capacity, expected_frags, want_index, summary_on_error):
+        """submit() and bam_submit(): call(out_index, out_summary, batch_out) is the library's; s its empty summary."""
+        arrs, ia = self._host_index() if want_index else (None, None)
+        reads, frags, bo = self._results(frag_capacity, expected_frags)
+        self._chk(call(C.byref(ia) if want_index else None, C.byref(s), C.byref(bo)), s if summary_on_error else None)
+        n = s.n_records
+        return (self._clip(arrs, n) if want_index else None), s.as_dict(), reads[:n].copy(), frags[:bo.n_frags].copy()
+
     def submit(self, ctx, text, fasta=False, final=True, frag_capacity=None, want_index=True):
         """Text in, filter results out: (Index or None, summary dict, reads, frags) for the regular prefix of `text`,
         through `ctx` (a capi.Context of the same device and the same build; no_qual for FASTA)."""
         t = _as_u8(text)
-        if frag_capacity is None:
-            frag_capacity = t.size // 100 + self.max_records + 16
-        arrs, ia = self._host_index() if want_index else (None, None)
-        reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
-        frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
-        bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
-        s = Summary()
-        self._chk(self.lib.tgsf_text_submit(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final),
-                                            C.byref(ia) if want_index else None, C.byref(s), C.byref(bo)))
-        n = s.n_records
-        return (self._clip(arrs, n) if want_index else None), s.as_dict(), reads[:n].copy(), frags[:bo.n_frags].copy()
+        return self._submit(lambda *a: self.lib.tgsf_text_submit(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final), *a),
+                            Summary(), frag_capacity, t.size // 100, want_index, False)
 
     # ---- the output side: the kept records as clean FASTQ / FASTA text ------------------------------------------------
     def reserve_output(self, max_frags, max_out_bytes):
@@ -276,14 +290,8 @@ class TextIndexer:
         s = OutSummary()
         rc = self.lib.tgsf_text_format(self.h, int(n_records), int(fasta), reads.ctypes.data, frags.ctypes.data, len(frags), int(fastq_out),
                                        out.ctypes.data, cap, rec_end.ctypes.data, C.byref(s))
-        self._chk_out(rc, s)
+        self._chk(rc, s)
         return out[:s.n_bytes].tobytes(), rec_end[:s.n_records].copy(), s.as_dict()
-
-    def _chk_out(self, rc, s):
-        if rc != 0:
-            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
-            e.summary = s.as_dict()
-            raise e
 
     def format_device(self, n_records, d_reads, d_frags, n_frags, fastq_out=True, fasta=False, d_text=None, d_index: IndexArrays | None = None,
                       d_out=None, out_capacity=0, d_rec_end=None, d_summary=None, stream=None):
@@ -299,29 +307,28 @@ class TextIndexer:
         self._chk(self.lib.tgsf_text_out_stage_ms(self.h, C.byref(ms)))
         return {"sizes": ms[0], "layout": ms[1], "copy": ms[2]}
 
+    def _filter(self, call, si, out, out_capacity, frag_capacity, expected_frags, want_results, in_summary_on_error):
+        """filter() and bam_filter(): call(out, out_capacity, rec_end, out_summary, in_summary, out_index, batch_out) is the
+        library's; si its empty input summary."""
+        out, cap = self._out(out, out_capacity)
+        rec_end = np.zeros(max(getattr(self, "max_frags", 0), 1), np.uint64)
+        so = OutSummary()
+        reads, frags, bo = self._results(frag_capacity, expected_frags) if want_results else (None, None, None)
+        rc = call(out.ctypes.data, cap, rec_end.ctypes.data, C.byref(so), C.byref(si), None, C.byref(bo) if want_results else None)
+        self._chk(rc, so, si if in_summary_on_error else None)
+        res = (out[:so.n_bytes].tobytes(), rec_end[:so.n_records].copy(), so.as_dict(), si.as_dict())
+        if want_results:
+            res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
+        return res
+
     def filter(self, ctx, text, fasta=False, final=True, fastq_out=None, out=None, out_capacity=None, frag_capacity=None, want_results=False):
         """Text in, clean text out: (the text as bytes, rec_end, out summary dict, in summary dict) for the regular prefix
         of `text`; with want_results also the per-read records and the fragments, as submit() returns them."""
         t = _as_u8(text)
         if fastq_out is None:
             fastq_out = not fasta
-        out, cap = self._out(out, out_capacity)
-        rec_end = np.zeros(max(getattr(self, "max_frags", 0), 1), np.uint64)
-        so, si = OutSummary(), Summary()
-        bo = reads = frags = None
-        if want_results:
-            if frag_capacity is None:
-                frag_capacity = t.size // 100 + self.max_records + 16
-            reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
-            frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
-            bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
-        rc = self.lib.tgsf_text_filter(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final), int(fastq_out), out.ctypes.data, cap,
-                                       rec_end.ctypes.data, C.byref(so), C.byref(si), None, C.byref(bo) if bo is not None else None)
-        self._chk_out(rc, so)
-        res = (out[:so.n_bytes].tobytes(), rec_end[:so.n_records].copy(), so.as_dict(), si.as_dict())
-        if want_results:
-            res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
-        return res
+        return self._filter(lambda *a: self.lib.tgsf_text_filter(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final), int(fastq_out), *a),
+                            Summary(), out, out_capacity, frag_capacity, t.size // 100, want_results, False)
 
     # ---- the BAM input side: inflated unaligned BAM records in -----------------------------------------------------------
     def reserve_bam(self, max_bam_bytes):
@@ -346,49 +353,16 @@ class TextIndexer:
         self._chk(self.lib.tgsf_text_bam_decode_device(self.h, d_bam, int(n_bytes), int(final), rec_off.ctypes.data, rec_off.size - 1, int(walk_stop),
                                                        C.byref(d_index) if d_index is not None else None, d_summary, stream))
 
-    def _chk_bam(self, rc, s):
-        if rc != 0:
-            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
-            e.summary = s.as_dict()
-            raise e
-
     def bam_submit(self, ctx, bam, final=True, frag_capacity=None, want_index=True):
         """BAM in, filter results out: (Index or None, summary dict, reads, frags) for the indexed prefix of `bam`.  A quality
         byte of 233 raises TgsfError(-6); its `summary` attribute holds bad_qual."""
         b = _as_u8(bam)
-        if frag_capacity is None:
-            frag_capacity = b.size // 50 + self.max_records + 16
-        arrs, ia = self._host_index() if want_index else (None, None)
-        reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
-        frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
-        bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
-        s = BamSummary()
-        rc = self.lib.tgsf_text_bam_submit(self.h, ctx.h, b.ctypes.data, b.size, int(final), C.byref(ia) if want_index else None, C.byref(s), C.byref(bo))
-        self._chk_bam(rc, s)
-        n = s.n_records
-        return (self._clip(arrs, n) if want_index else None), s.as_dict(), reads[:n].copy(), frags[:bo.n_frags].copy()
+        return self._submit(lambda *a: self.lib.tgsf_text_bam_submit(self.h, ctx.h, b.ctypes.data, b.size, int(final), *a),
+                            BamSummary(), frag_capacity, b.size // 50, want_index, True)
 
     def bam_filter(self, ctx, bam, final=True, fastq_out=True, out=None, out_capacity=None, frag_capacity=None, want_results=False):
         """BAM in, clean text out: (the text as bytes, rec_end, out summary dict, BAM summary dict) for the indexed prefix of
         `bam`; with want_results also the per-read records and the fragments, as bam_submit() returns them."""
         b = _as_u8(bam)
-        out, cap = self._out(out, out_capacity)
-        rec_end = np.zeros(max(getattr(self, "max_frags", 0), 1), np.uint64)
-        so, si = OutSummary(), BamSummary()
-        bo = reads = frags = None
-        if want_results:
-            if frag_capacity is None:
-                frag_capacity = b.size // 50 + self.max_records + 16
-            reads = np.zeros(self.max_records, dtype=abi.READ_RESULT_DTYPE)
-            frags = np.zeros(frag_capacity, dtype=abi.FRAGMENT_DTYPE)
-            bo = abi.BatchOut(reads.ctypes.data, frags.ctypes.data, frag_capacity, 0)
-        rc = self.lib.tgsf_text_bam_filter(self.h, ctx.h, b.ctypes.data, b.size, int(final), int(fastq_out), out.ctypes.data, cap,
-                                           rec_end.ctypes.data, C.byref(so), C.byref(si), None, C.byref(bo) if bo is not None else None)
-        if rc != 0:
-            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
-            e.summary, e.in_summary = so.as_dict(), si.as_dict()
-            raise e
-        res = (out[:so.n_bytes].tobytes(), rec_end[:so.n_records].copy(), so.as_dict(), si.as_dict())
-        if want_results:
-            res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
-        return res
+        return self._filter(lambda *a: self.lib.tgsf_text_bam_filter(self.h, ctx.h, b.ctypes.data, b.size, int(final), int(fastq_out), *a),
+                            BamSummary(), out, out_capacity, frag_capacity, b.size // 50, want_results, True)
