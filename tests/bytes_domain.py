@@ -355,7 +355,7 @@ def myers(lib_path, name, env, monkeypatch):
         ctx.close()
 
 
-ALIGN_CLASSES = {"two_words": ("dword", "filter45"), "four_words": ("words",), "wide": ("wide",)}      # k_align_windows<2 | 4 | wide>
+ALIGN_CLASSES = {"two_words": ("dword", "filter45"), "four_words": ("words",), "wide": ("wide",)}      # k_align_windows<2 | 4 | kWideNW>: up to the column forms Bv<2>, Bv<4>, BvW
 
 
 def align_windows(lib_path, cls, n):

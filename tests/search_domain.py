@@ -536,6 +536,7 @@ assert all(len(s) <= 32 for s, _ in SETS.values()) and sum(len(s) == 32 for s, _
 SET_ENVS = {"default": {}, "pool3": {"TGSF_POOL_CAP": "3"}, "segments": {"TGSF_MID_FLAT": "0"}, "segments_pool3": {"TGSF_MID_FLAT": "0", "TGSF_POOL_CAP": "3"},
             "filter0": {"TGSF_MID_FILTER": "0"}, "filter1": {"TGSF_MID_FILTER": "1"}, "filter2": {"TGSF_MID_FILTER": "2"}}
 SET_CASES = [(name, "default") for name in SETS] + [(name, env) for name in ("runs32", "lengths32", "suffix32") for env in SET_ENVS if env != "default"]
+SET_CASES.append(("wide32", "pool3"))     # the wide column through the count-and-rescan path and the per-slot resolve
 SET_READS = 96
 
 

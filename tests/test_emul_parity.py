@@ -213,7 +213,7 @@ def test_emul_candidate_pool_overflow_is_handled(emul, adapters, m_mid, order, m
 
 
 @pytest.mark.parametrize("order", ["forward", "reverse"])
-@pytest.mark.parametrize("name", ["ont_zoo", "hifi_zoo", "ont_m1", "huge_adapter"])
+@pytest.mark.parametrize("name", ["ont_zoo", "hifi_zoo", "ont_m1", "huge_adapter", "wide_adapter"])
 def test_emul_golden_through_the_overflow_path(emul, golden_dir, name, order, monkeypatch, capfd):
     """A pool of 2 slots: every batch with more than two candidates takes the count-and-rescan path; the goldens must not notice."""
     monkeypatch.setenv("TGSF_POOL_CAP", "2")

@@ -280,7 +280,7 @@ def test_gpu_candidate_pool_overflow_is_handled(adapters, m_mid, long_len, monke
     ctx.close()
 
 
-@pytest.mark.parametrize("name", ["ont_zoo", "hifi_zoo", "ont_m1", "huge_adapter", "ont_trim"])
+@pytest.mark.parametrize("name", ["ont_zoo", "hifi_zoo", "ont_m1", "huge_adapter", "ont_trim", "wide_adapter"])
 def test_gpu_golden_through_the_overflow_path(golden_dir, name, monkeypatch, capfd):
     monkeypatch.setenv("TGSF_POOL_CAP", "2")
     monkeypatch.setenv("TGSF_TRACE_POOL", "1")

@@ -41,36 +41,75 @@ constexpr int kSuffixMaxK = 12;    // adapters of 33..64 bp searched within at m
 // Bit-vector edit distance, standard layout: row r of the adapter is bit r%64 of
 // word r/64.  Rows >= Q of the last word are don't-care (information only moves
 // towards higher bits).  Used by every off-the-hot-loop search (end windows,
-// start locations) and by adapters of 65..256 bp in the middle scan.
+// start locations, paths) and by adapters beyond 64 bp in the middle scan.
+//
+// The column has two forms, and everything below the hot scans is written once
+// over either.  Bv<NW>: NW = 1..4 words in registers, every loop over them fully
+// unrolled; its Peq tables are peq_fwd / peq_rev, kPeqW words a symbol (adapters
+// up to 256 bp).  BvW: kWideNW-word arrays walked by run-time loops, ceil(Q / 64)
+// words of them in use (they live in scratch memory: correct for any length up to
+// kMaxQ, not fast -- such adapters, only reachable with -a, are a corner of the
+// domain; the reference's multi-block edlib accepts them, include/edlib.cpp:182-185);
+// its tables are peq_fwd_w / peq_rev_w, kWideNW words a symbol.
 // ---------------------------------------------------------------------------
 template <int NW>
 struct Bv {
+    static constexpr bool kWide = false;
+    static constexpr int kWords = NW;        // words the form holds
+    static constexpr int kStride = kPeqW;    // words per symbol in its Peq tables
+    TGSF_HD static constexpr int words(int /*Q*/) { return NW; }
     uint64_t p[NW], m[NW];
     int score;           // value of row Q in the current column
 };
+struct BvW {
+    static constexpr bool kWide = true;
+    static constexpr int kWords = kWideNW;
+    static constexpr int kStride = kWideNW;
+    TGSF_HD static int words(int Q) { return (Q + 63) >> 6; }
+    uint64_t p[kWideNW], m[kWideNW];
+    int score;
+};
 
-template <int NW>
-TGSF_HD void bv_init(Bv<NW>& s, int Q) {
-#pragma unroll
-    for (int w = 0; w < NW; w++) { s.p[w] = ~0ull; s.m[w] = 0ull; }
+// (The loops over the words carry no unroll pragma: it would reshape the wide form's run-time loops too.  The register
+// form's word count is a constant of at most 4, and the compiler unrolls those fully by itself.)
+template <class Col>
+TGSF_HD void bv_init(Col& s, int Q) {
+    const int nw = Col::words(Q);
+    for (int w = 0; w < nw; w++) { s.p[w] = ~0ull; s.m[w] = 0ull; }
     s.score = Q;
 }
 
-// One text column.  eq[w]: rows equal to the text symbol.  hin_top: horizontal
-// delta entering row 1: 0 for an infix search (free start, edlib.cpp:584), +1 for
-// prefix/global searches.
-template <int NW>
-TGSF_HD void bv_step(Bv<NW>& s, const uint64_t* eq, int hin_top, int Q) {
+// 64 rows of a RANGE of the adapter (from row q0 + 64 w on) for one symbol; `row`: the symbol's kWideNW words of the wide
+// table.  Rows below the range come along in the last word: they sit below every row that counts (carries run downwards).
+TGSF_HD uint64_t eq_range(const uint64_t* row, int q0, int w) {
+    const int bit = q0 + 64 * w, wi = bit >> 6, sh = bit & 63;
+    uint64_t v = wi < kWideNW ? row[wi] >> sh : 0ull;
+    if (sh && wi + 1 < kWideNW) v |= row[wi + 1] << (64 - sh);
+    return v;
+}
+// the rows from q0 on of a symbol's row of the wide table, as an Eq-word source of bv_step
+struct EqRange {
+    const uint64_t* row;
+    int q0;
+    TGSF_HD uint64_t operator[](int w) const { return eq_range(row, q0, w); }
+};
+
+// One text column.  eq[w]: rows equal to the text symbol (a symbol's row of the column's table, or an EqRange of it:
+// then Q counts the rows of the range).  hin_top: horizontal delta entering row 1: 0 for an infix search (free start,
+// edlib.cpp:584), +1 for prefix/global searches.  ph_out (optional): the horizontal +1 words of the column.
+template <class Col, class EqSrc>
+TGSF_HD void bv_step(Col& s, EqSrc eq, int hin_top, int Q, uint64_t* ph_out = nullptr) {
+    const int nw = Col::words(Q);
     int hin = hin_top;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
+    for (int w = 0; w < nw; w++) {
         uint64_t Eq = eq[w], Pv = s.p[w], Mv = s.m[w];
         uint64_t Xv = Eq | Mv;
         if (hin < 0) Eq |= 1ull;
         uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
         uint64_t Ph = Mv | ~(Xh | Pv);
         uint64_t Mh = Pv & Xh;
-        const int bit = (w == NW - 1) ? ((Q - 1) & 63) : 63;
+        if (ph_out) ph_out[w] = Ph;
+        const int bit = (w == nw - 1) ? ((Q - 1) & 63) : 63;
         int hout = (int)((Ph >> bit) & 1ull) - (int)((Mh >> bit) & 1ull);
         Ph <<= 1; Mh <<= 1;
         if (hin < 0) Mh |= 1ull;

@@ -1027,30 +1027,11 @@ struct WinAln {
     int mlen;          // alignmentLength - editDistance of the first location
 };
 
-// one text column in global mode (hin = +1 at the top); returns the horizontal +1 words
-template <int NW>
-TGSF_HD void bv_step_global(Bv<NW>& s, const uint64_t* eq, uint64_t* ph_out, int Q) {
-    int hin = 1;
-#pragma unroll
-    for (int w = 0; w < NW; w++) {
-        uint64_t Eq = eq[w], Pv = s.p[w], Mv = s.m[w];
-        uint64_t Xv = Eq | Mv;
-        if (hin < 0) Eq |= 1ull;
-        uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-        uint64_t Ph = Mv | ~(Xh | Pv);
-        uint64_t Mh = Pv & Xh;
-        ph_out[w] = Ph;
-        const int bit = (w == NW - 1) ? ((Q - 1) & 63) : 63;
-        int hout = (int)((Ph >> bit) & 1ull) - (int)((Mh >> bit) & 1ull);
-        Ph <<= 1; Mh <<= 1;
-        if (hin < 0) Mh |= 1ull;
-        if (hin > 0) Ph |= 1ull;
-        s.p[w] = Mh | ~(Xv | Ph);
-        s.m[w] = Ph & Xv;
-        hin = hout;
-    }
-    s.score += hin;
-}
+// the Peq tables of adapter a for a column form (see Bv, BvW): Col::kStride words a symbol
+template <class Col>
+TGSF_D const uint64_t* peq_fwd_of(const DevParams& P, int a) { return (Col::kWide ? P.peq_fwd_w : P.peq_fwd) + (size_t)a * 256 * Col::kStride; }
+template <class Col>
+TGSF_D const uint64_t* peq_rev_of(const DevParams& P, int a) { return (Col::kWide ? P.peq_rev_w : P.peq_rev) + (size_t)a * 256 * Col::kStride; }
 
 // lane-private scratch: word k of column j of this lane
 struct LaneScratch {
@@ -1058,32 +1039,30 @@ struct LaneScratch {
     TGSF_HD uint64_t& at(int j, int k, int nwords) const { return base[((size_t)j * nwords + k) * 64]; }
 };
 
-// number of columns of the canonical global alignment of the adapter against t[0..T)
-template <int NW>
-TGSF_D int path_len_bv(const uint64_t* pf /*[256][2]*/, int Q, const uint8_t* t, int T, LaneScratch sc)
+// columns of the path edlib's traceback takes through the global alignment of Q adapter rows against t[0, T): from the
+// bottom-right cell, up before left before diagonal (include/edlib.cpp:1023 / 1057 / 1088).  eq_of(symbol): the Eq words
+// of those rows (the symbol's row of the column's forward table, or an EqRange of it).
+template <class Col, class EqOf>
+TGSF_D int path_columns(int Q, const uint8_t* t, int T, LaneScratch sc, EqOf eq_of)
 {
-    Bv<NW> s;
+    const int nw = Col::words(Q);
+    Col s;
     bv_init(s, Q);
     for (int j = 1; j <= T; j++) {
-        uint64_t ph[NW];
-        bv_step_global<NW>(s, pf + (size_t)t[j - 1] * kPeqW, ph, Q);
-#pragma unroll
-        for (int w = 0; w < NW; w++) { sc.at(j, w, 2 * NW) = s.p[w]; sc.at(j, NW + w, 2 * NW) = ph[w]; }
+        uint64_t ph[Col::kWords];
+        bv_step(s, eq_of(t[j - 1]), 1, Q, ph);
+        for (int w = 0; w < nw; w++) { sc.at(j, w, 2 * nw) = s.p[w]; sc.at(j, nw + w, 2 * nw) = ph[w]; }
     }
     int i = Q, j = T, len = 0;
     while (i > 0 && j > 0) {
         const int r = i - 1;
-        const uint64_t pv = sc.at(j, r >> 6, 2 * NW);
-        if ((pv >> (r & 63)) & 1ull) { i--; }
-        else {
-            const uint64_t ph = sc.at(j, NW + (r >> 6), 2 * NW);
-            if ((ph >> (r & 63)) & 1ull) j--; else { i--; j--; }
-        }
+        if ((sc.at(j, r >> 6, 2 * nw) >> (r & 63)) & 1ull) { i--; }
+        else if ((sc.at(j, nw + (r >> 6), 2 * nw) >> (r & 63)) & 1ull) j--;
+        else { i--; j--; }
         len++;
     }
     return len + i + j;        // straight along the border (edlib.cpp:1028-1032, :1062-1067)
 }
-
 
 // The bytes of a window, sixteen per load (any alignment; whole chunks only, the tail byte by byte): fn(j, byte).
 // One lane walks its own window, so a load per byte would put the memory latency on every column.  (Fetching the
@@ -1116,195 +1095,33 @@ TGSF_D void each_byte_bwd(const uint8_t* t, int end, int n, F fn)
     for (; l < n; l++) fn(l, (uint32_t)t[end - l]);
 }
 
-template <int NW>
+// ---- the four searches, over either form of the column (Bv<NW>, BvW: tgsf_core.h) ----
+// start of the location ending at column `end` with distance `best`: the longest prefix search backwards (edlib.cpp:223-258)
+template <class Col>
 TGSF_D int start_of(const DevParams& P, int a, const uint8_t* t, int end, int best)
 {
     const int Q = P.Q[a];
-    const uint64_t* pr = P.peq_rev + (size_t)a * 256 * kPeqW;
-    Bv<NW> b;
+    const uint64_t* pr = peq_rev_of<Col>(P, a);
+    Col b;
     bv_init(b, Q);
     int maxl = end + 1;
     if (maxl > Q + best) maxl = Q + best;
     int best_l = 1;
-    if constexpr (NW == 1) {
+    if constexpr (Col::kWords == 1) {
         each_byte_bwd(t, end, maxl, [&](int l, uint32_t sym) TGSF_INLINE_LAMBDA {
-            bv_step<NW>(b, pr + (size_t)sym * kPeqW, 1, Q);
+            bv_step(b, pr + (size_t)sym * Col::kStride, 1, Q);
             if (b.score == best) best_l = l + 1;
         });
     } else {
         for (int l = 1; l <= maxl; l++) {
-            bv_step<NW>(b, pr + (size_t)t[end - (l - 1)] * kPeqW, 1, Q);
+            bv_step(b, pr + (size_t)t[end - (l - 1)] * Col::kStride, 1, Q);
             if (b.score == best) best_l = l;
         }
     }
     return end - best_l + 1;
 }
 
-// mlen of the first location, or -1 when the bounds prove it is below `need`
-// (the caller only compares mlen with need), or a value >= need when they prove that.
-template <int NW>
-TGSF_D int first_mlen(const DevParams& P, int a, const uint8_t* t, int start0, int end0, int best, int need,
-                      LaneScratch sc, bool exact)
-{
-    const int Q = P.Q[a];
-    const int T = end0 - start0 + 1;
-    if (!exact) {
-        const int lo = T - best + (Q > T ? Q - T : 0);
-        const int slack = best - (T - Q);
-        const int hi = T - best + (slack > 0 ? slack / 2 : 0);
-        if (lo >= need) return lo;          // passes whatever the path
-        if (hi < need) return -1;           // fails whatever the path
-    }
-    return path_len_bv<NW>(P.peq_fwd + (size_t)a * 256 * kPeqW, Q, t + start0, T, sc) - best;
-}
-
-template <int NW>
-TGSF_D WinAln align_window(const DevParams& P, int a, const uint8_t* t, int T, int kk, int need, LaneScratch sc, bool exact)
-{
-    const int Q = P.Q[a];
-    const uint64_t* pf = P.peq_fwd + (size_t)a * 256 * kPeqW;
-    WinAln r;
-    r.best = -1; r.n = 0; r.first_end = r.last_end = -1; r.start0 = 0; r.mlen = 0;
-    // peq tables are [256][kPeqW]; only the first NW words of each symbol are used
-    Bv<NW> s;
-    bv_init(s, Q);
-    int cur = kk + 1;
-    auto column = [&](int j, uint32_t sym) TGSF_INLINE_LAMBDA {
-        bv_step<NW>(s, pf + (size_t)sym * kPeqW, 0, Q);
-        if (s.score < cur) { cur = s.score; r.first_end = j; r.n = 0; }
-        if (s.score == cur && cur <= kk) { r.last_end = j; r.n++; }
-    };
-    if constexpr (NW == 1) each_byte_fwd(t, T, column);
-    else for (int j = 0; j < T; j++) column(j, (uint32_t)t[j]);
-    if (cur > kk) return r;
-    r.best = cur;
-    r.start0 = start_of<NW>(P, a, t, r.first_end, cur);          // edlib.cpp:246-255
-    r.mlen = first_mlen<NW>(P, a, t, r.start0, r.first_end, cur, need, sc, exact);
-    return r;
-}
-
-// smallest start over all locations of a window whose optimum is `best`
-template <int NW>
-TGSF_D int min_start_all(const DevParams& P, int a, const uint8_t* t, int T, int best)
-{
-    const int Q = P.Q[a];
-    const uint64_t* pf = P.peq_fwd + (size_t)a * 256 * kPeqW;
-    Bv<NW> s;
-    bv_init(s, Q);
-    int mn = T;
-    for (int j = 0; j < T; j++) {
-        bv_step<NW>(s, pf + (size_t)t[j] * kPeqW, 0, Q);
-        if (s.score == best) {
-            int st = start_of<NW>(P, a, t, j, best);
-            mn = st < mn ? st : mn;
-        }
-    }
-    return mn;
-}
-
-// ---------------------------------------------------------------------------
-// Adapters beyond 256 bp (only reachable with -a): the same searches with the column in kWideNW-word arrays walked by
-// run-time loops (they live in scratch memory: correct for any length up to kMaxQ, not fast -- such adapters are a
-// corner of the domain, the reference's multi-block edlib accepts them, include/edlib.cpp:182-185).
-// ---------------------------------------------------------------------------
-struct BvW {
-    uint64_t p[kWideNW], m[kWideNW];
-    int score;
-};
-TGSF_D void bvw_init(BvW& s, int Q, int nw) {
-    for (int w = 0; w < nw; w++) { s.p[w] = ~0ull; s.m[w] = 0ull; }
-    s.score = Q;
-}
-// one text column; hin_top 0 (infix) or +1 (prefix / global); ph_out (optional): the horizontal +1 words
-TGSF_D void bvw_step(BvW& s, const uint64_t* eq, int hin_top, int Q, int nw, uint64_t* ph_out) {
-    int hin = hin_top;
-    for (int w = 0; w < nw; w++) {
-        uint64_t Eq = eq[w], Pv = s.p[w], Mv = s.m[w];
-        uint64_t Xv = Eq | Mv;
-        if (hin < 0) Eq |= 1ull;
-        uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-        uint64_t Ph = Mv | ~(Xh | Pv);
-        uint64_t Mh = Pv & Xh;
-        if (ph_out) ph_out[w] = Ph;
-        const int bit = (w == nw - 1) ? ((Q - 1) & 63) : 63;
-        int hout = (int)((Ph >> bit) & 1ull) - (int)((Mh >> bit) & 1ull);
-        Ph <<= 1; Mh <<= 1;
-        if (hin < 0) Mh |= 1ull;
-        if (hin > 0) Ph |= 1ull;
-        s.p[w] = Mh | ~(Xv | Ph);
-        s.m[w] = Ph & Xv;
-        hin = hout;
-    }
-    s.score += hin;
-}
-TGSF_D int start_of_w(const DevParams& P, int a, const uint8_t* t, int end, int best)
-{
-    const int Q = P.Q[a], nw = (Q + 63) >> 6;
-    const uint64_t* pr = P.peq_rev_w + (size_t)a * 256 * kWideNW;
-    BvW b;
-    bvw_init(b, Q, nw);
-    int maxl = end + 1;
-    if (maxl > Q + best) maxl = Q + best;
-    int best_l = 1;
-    for (int l = 1; l <= maxl; l++) {
-        bvw_step(b, pr + (size_t)t[end - (l - 1)] * kWideNW, 1, Q, nw, nullptr);
-        if (b.score == best) best_l = l;
-    }
-    return end - best_l + 1;
-}
 // ---- the path of the first location beyond 1 MiB of traceback state: Hirschberg's divide and conquer as edlib does it ----
-// 64 rows of a RANGE of the adapter (from row q0 + 64 w on) for one symbol; `row`: the symbol's kWideNW words of the wide
-// table.  Rows below the range come along in the last word: they sit below every row that counts (carries run downwards).
-TGSF_D uint64_t eq_range(const uint64_t* row, int q0, int w) {
-    const int bit = q0 + 64 * w, wi = bit >> 6, sh = bit & 63;
-    uint64_t v = wi < kWideNW ? row[wi] >> sh : 0ull;
-    if (sh && wi + 1 < kWideNW) v |= row[wi + 1] << (64 - sh);
-    return v;
-}
-// one text column of the GLOBAL alignment (hin = +1 at the top) of the Qn adapter rows from row q0 on
-TGSF_D void bvw_step_range(BvW& s, const uint64_t* row, int q0, int Qn, int nw, uint64_t* ph_out) {
-    int hin = 1;
-    for (int w = 0; w < nw; w++) {
-        uint64_t Eq = eq_range(row, q0, w), Pv = s.p[w], Mv = s.m[w];
-        uint64_t Xv = Eq | Mv;
-        if (hin < 0) Eq |= 1ull;
-        uint64_t Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-        uint64_t Ph = Mv | ~(Xh | Pv);
-        uint64_t Mh = Pv & Xh;
-        if (ph_out) ph_out[w] = Ph;
-        const int bit = (w == nw - 1) ? ((Qn - 1) & 63) : 63;
-        int hout = (int)((Ph >> bit) & 1ull) - (int)((Mh >> bit) & 1ull);
-        Ph <<= 1; Mh <<= 1;
-        if (hin < 0) Mh |= 1ull;
-        if (hin > 0) Ph |= 1ull;
-        s.p[w] = Mh | ~(Xv | Ph);
-        s.m[w] = Ph & Xv;
-        hin = hout;
-    }
-    s.score += hin;
-}
-// columns of the path edlib's traceback takes through the global alignment of adapter rows [q0, q0 + Qn) against
-// t[0, Tn): from the bottom-right cell, up before left before diagonal (include/edlib.cpp:1023 / 1057 / 1088)
-TGSF_D int path_columns_range(const uint64_t* pf, int q0, int Qn, const uint8_t* t, int Tn, LaneScratch sc)
-{
-    const int nw = (Qn + 63) >> 6;
-    BvW s;
-    bvw_init(s, Qn, nw);
-    uint64_t ph[kWideNW];
-    for (int j = 1; j <= Tn; j++) {
-        bvw_step_range(s, pf + (size_t)t[j - 1] * kWideNW, q0, Qn, nw, ph);
-        for (int w = 0; w < nw; w++) { sc.at(j, w, 2 * nw) = s.p[w]; sc.at(j, nw + w, 2 * nw) = ph[w]; }
-    }
-    int i = Qn, j = Tn, len = 0;
-    while (i > 0 && j > 0) {
-        const int r = i - 1;
-        if ((sc.at(j, r >> 6, 2 * nw) >> (r & 63)) & 1ull) { i--; }
-        else if ((sc.at(j, nw + (r >> 6), 2 * nw) >> (r & 63)) & 1ull) j--;
-        else { i--; j--; }
-        len++;
-    }
-    return len + i + j;
-}
 // alignmentLength of edlib's path for adapter a against t[0, T) with distance `best` (obtainAlignment,
 // include/edlib.cpp:1164-1216): by traceback while (2*8+4)*blocks*columns + 8*columns < 1 MiB (:1191-1193), else the
 // target is cut in the middle (:1250-1251), the query at the SMALLEST row h in 1..Qn-1 whose two half scores
@@ -1317,8 +1134,8 @@ TGSF_D int path_columns_range(const uint64_t* pf, int q0, int Qn, const uint8_t*
 TGSF_D int alignment_length_w(const DevParams& P, int a, const uint8_t* t, int T, int best, LaneScratch sc)
 {
     const int Q = P.Q[a];
-    const uint64_t* pf = P.peq_fwd_w + (size_t)a * 256 * kWideNW;
-    const uint64_t* pr = P.peq_rev_w + (size_t)a * 256 * kWideNW;
+    const uint64_t* pf = peq_fwd_of<BvW>(P, a);
+    const uint64_t* pr = peq_rev_of<BvW>(P, a);
     struct Node { int q0, qn, t0, tn, best; };
     Node st[40];
     int sp = 0, total = 0;
@@ -1326,19 +1143,22 @@ TGSF_D int alignment_length_w(const DevParams& P, int a, const uint8_t* t, int T
     while (sp > 0) {
         const Node nd = st[--sp];
         if (nd.qn == 0 || nd.tn == 0) { total += nd.qn + nd.tn; continue; }                       // :1171-1179
-        const int nw = (nd.qn + 63) >> 6;
+        const int nw = BvW::words(nd.qn);
         const long long data = (2ll * 8 + 4) * nw * nd.tn + 8ll * nd.tn;
-        if (data < (1ll << 20)) { total += path_columns_range(pf, nd.q0, nd.qn, t + nd.t0, nd.tn, sc); continue; }
+        if (data < (1ll << 20)) {
+            total += path_columns<BvW>(nd.qn, t + nd.t0, nd.tn, sc, [pf, q0 = nd.q0](uint32_t sym) TGSF_INLINE_LAMBDA { return EqRange{pf + (size_t)sym * kWideNW, q0}; });
+            continue;
+        }
         const int lw = nd.tn / 2, rw = nd.tn - lw;
         BvW s;
-        bvw_init(s, nd.qn, nw);
-        for (int j = 0; j < lw; j++) bvw_step_range(s, pf + (size_t)t[nd.t0 + j] * kWideNW, nd.q0, nd.qn, nw, nullptr);
+        bv_init(s, nd.qn);
+        for (int j = 0; j < lw; j++) bv_step(s, EqRange{pf + (size_t)t[nd.t0 + j] * kWideNW, nd.q0}, 1, nd.qn);
         for (int w = 0; w < nw; w++) { sc.at(0, w, 1) = s.p[w]; sc.at(0, nw + w, 1) = s.m[w]; }     // the left half's last column
         // the right half: the reversed rows against the reversed text (rows [q0, q0+qn) reversed = rows
         // [Q - q0 - qn, Q - q0) of the reversed adapter)
-        bvw_init(s, nd.qn, nw);
+        bv_init(s, nd.qn);
         const int q0r = Q - nd.q0 - nd.qn;
-        for (int j = 0; j < rw; j++) bvw_step_range(s, pr + (size_t)t[nd.t0 + nd.tn - 1 - j] * kWideNW, q0r, nd.qn, nw, nullptr);
+        for (int j = 0; j < rw; j++) bv_step(s, EqRange{pr + (size_t)t[nd.t0 + nd.tn - 1 - j] * kWideNW, q0r}, 1, nd.qn);
         auto dl = [&](int i) { return (int)((sc.at(0, i >> 6, 1) >> (i & 63)) & 1ull) - (int)((sc.at(0, nw + (i >> 6), 1) >> (i & 63)) & 1ull); };
         auto dr = [&](int i) { return (int)((s.p[i >> 6] >> (i & 63)) & 1ull) - (int)((s.m[i >> 6] >> (i & 63)) & 1ull); };
         int Rm = rw;                                    // R[1]: the last qn - 1 rows against the right half
@@ -1363,70 +1183,72 @@ TGSF_D int alignment_length_w(const DevParams& P, int a, const uint8_t* t, int T
     return total;
 }
 
-TGSF_D int first_mlen_w(const DevParams& P, int a, const uint8_t* t, int start0, int end0, int best, int need, LaneScratch sc, bool exact)
+// mlen of the first location, or -1 when the bounds prove it is below `need`
+// (the caller only compares mlen with need), or a value >= need when they prove that.
+template <class Col>
+TGSF_D int first_mlen(const DevParams& P, int a, const uint8_t* t, int start0, int end0, int best, int need,
+                      LaneScratch sc, bool exact)
 {
-    const int Q = P.Q[a], nw = (Q + 63) >> 6;
+    const int Q = P.Q[a];
     const int T = end0 - start0 + 1;
     if (!exact) {
         const int lo = T - best + (Q > T ? Q - T : 0);
         const int slack = best - (T - Q);
         const int hi = T - best + (slack > 0 ? slack / 2 : 0);
-        if (lo >= need) return lo;
-        if (hi < need) return -1;
+        if (lo >= need) return lo;          // passes whatever the path
+        if (hi < need) return -1;           // fails whatever the path
     }
-    if ((2ll * 8 + 4) * nw * T + 8ll * T >= (1ll << 20)) {                 // beyond 1 MiB of traceback state: as edlib, include/edlib.cpp:1191-1210
-        const int len = alignment_length_w(P, a, t + start0, T, best, sc);
-        return len < 0 ? -1 : len - best;
+    if constexpr (Col::kWide) {
+        if ((2ll * 8 + 4) * Col::words(Q) * T + 8ll * T >= (1ll << 20)) {     // beyond 1 MiB of traceback state: as edlib, include/edlib.cpp:1191-1210
+            const int len = alignment_length_w(P, a, t + start0, T, best, sc);
+            return len < 0 ? -1 : len - best;
+        }
     }
-    const uint64_t* pf = P.peq_fwd_w + (size_t)a * 256 * kWideNW;
-    const uint8_t* tt = t + start0;
-    BvW s;
-    bvw_init(s, Q, nw);
-    uint64_t ph[kWideNW];
-    for (int j = 1; j <= T; j++) {
-        bvw_step(s, pf + (size_t)tt[j - 1] * kWideNW, 1, Q, nw, ph);
-        for (int w = 0; w < nw; w++) { sc.at(j, w, 2 * nw) = s.p[w]; sc.at(j, nw + w, 2 * nw) = ph[w]; }
-    }
-    int i = Q, j = T, len = 0;
-    while (i > 0 && j > 0) {                              // up > left > diagonal (edlib.cpp:1023/1057/1088)
-        const int r = i - 1;
-        if ((sc.at(j, r >> 6, 2 * nw) >> (r & 63)) & 1ull) { i--; }
-        else if ((sc.at(j, nw + (r >> 6), 2 * nw) >> (r & 63)) & 1ull) j--;
-        else { i--; j--; }
-        len++;
-    }
-    return len + i + j - best;
+    // (the whole adapter: the table's rows as they are -- as an EqRange from row 0, two loads and two shifts a word, the wide
+    // k_end_windows took 8.4 ms against 7.6 on a batch with 300- and 700-bp adapters)
+    const uint64_t* pf = peq_fwd_of<Col>(P, a);
+    return path_columns<Col>(Q, t + start0, T, sc, [pf](uint32_t sym) TGSF_INLINE_LAMBDA { return pf + (size_t)sym * Col::kStride; }) - best;
 }
-TGSF_D WinAln align_window_w(const DevParams& P, int a, const uint8_t* t, int T, int kk, int need, LaneScratch sc, bool exact)
+
+template <class Col>
+TGSF_D WinAln align_window(const DevParams& P, int a, const uint8_t* t, int T, int kk, int need, LaneScratch sc, bool exact)
 {
-    const int Q = P.Q[a], nw = (Q + 63) >> 6;
-    const uint64_t* pf = P.peq_fwd_w + (size_t)a * 256 * kWideNW;
+    const int Q = P.Q[a];
+    const uint64_t* pf = peq_fwd_of<Col>(P, a);
     WinAln r;
     r.best = -1; r.n = 0; r.first_end = r.last_end = -1; r.start0 = 0; r.mlen = 0;
-    BvW s;
-    bvw_init(s, Q, nw);
+    Col s;
+    bv_init(s, Q);
     int cur = kk + 1;
-    for (int j = 0; j < T; j++) {
-        bvw_step(s, pf + (size_t)t[j] * kWideNW, 0, Q, nw, nullptr);
+    auto column = [&](int j, uint32_t sym) TGSF_INLINE_LAMBDA {
+        bv_step(s, pf + (size_t)sym * Col::kStride, 0, Q);
         if (s.score < cur) { cur = s.score; r.first_end = j; r.n = 0; }
         if (s.score == cur && cur <= kk) { r.last_end = j; r.n++; }
-    }
+    };
+    if constexpr (Col::kWords == 1) each_byte_fwd(t, T, column);
+    else for (int j = 0; j < T; j++) column(j, (uint32_t)t[j]);
     if (cur > kk) return r;
     r.best = cur;
-    r.start0 = start_of_w(P, a, t, r.first_end, cur);
-    r.mlen = first_mlen_w(P, a, t, r.start0, r.first_end, cur, need, sc, exact);
+    r.start0 = start_of<Col>(P, a, t, r.first_end, cur);          // edlib.cpp:246-255
+    r.mlen = first_mlen<Col>(P, a, t, r.start0, r.first_end, cur, need, sc, exact);
     return r;
 }
-TGSF_D int min_start_all_w(const DevParams& P, int a, const uint8_t* t, int T, int best)
+
+// smallest start over all locations of a window whose optimum is `best`
+template <class Col>
+TGSF_D int min_start_all(const DevParams& P, int a, const uint8_t* t, int T, int best)
 {
-    const int Q = P.Q[a], nw = (Q + 63) >> 6;
-    const uint64_t* pf = P.peq_fwd_w + (size_t)a * 256 * kWideNW;
-    BvW s;
-    bvw_init(s, Q, nw);
+    const int Q = P.Q[a];
+    const uint64_t* pf = peq_fwd_of<Col>(P, a);
+    Col s;
+    bv_init(s, Q);
     int mn = T;
     for (int j = 0; j < T; j++) {
-        bvw_step(s, pf + (size_t)t[j] * kWideNW, 0, Q, nw, nullptr);
-        if (s.score == best) { const int st = start_of_w(P, a, t, j, best); mn = st < mn ? st : mn; }
+        bv_step(s, pf + (size_t)t[j] * Col::kStride, 0, Q);
+        if (s.score == best) {
+            int st = start_of<Col>(P, a, t, j, best);
+            mn = st < mn ? st : mn;
+        }
     }
     return mn;
 }
@@ -1441,41 +1263,20 @@ TGSF_D LaneScratch lane_scratch(const DevBatch& B, size_t first_wave)
     return sc;
 }
 
-// Word count by adapter length = ceil(Q / 64): 1 (all library adapters), 2, and 3 or 4 (<= 256 bp; only kernels
-// instantiated with MAXNW = 4 carry that path -- they are launched when an adapter of the run needs it, so the
-// common configurations keep their register budget).
-template <int MAXNW>
-TGSF_D WinAln align_window_any(const DevParams& P, int a, const uint8_t* t, int T, int k, int need, const LaneScratch& sc, bool exact) {
-    const int Q = P.Q[a];
-    if (Q <= 64) return align_window<1>(P, a, t, T, k, need, sc, exact);
-    if constexpr (MAXNW > 4) { if (Q > 256) return align_window_w(P, a, t, T, k, need, sc, exact); }
-    if constexpr (MAXNW > 2) { if (Q > 192) return align_window<4>(P, a, t, T, k, need, sc, exact); if (Q > 128) return align_window<3>(P, a, t, T, k, need, sc, exact); }
-    return align_window<2>(P, a, t, T, k, need, sc, exact);
+// The column form by adapter length: ceil(Q / 64) = 1 (all library adapters), 2, and 3 or 4 words in registers
+// (<= 256 bp), the wide form beyond.  fn(Form<Col>{}) runs the search over that form.  Only kernels instantiated with
+// MAXNW = 4 carry the three- and four-word paths, only those with MAXNW = kWideNW the wide one -- they are launched when
+// an adapter of the run needs it, so the common configurations keep their register budget.
+// (The callers' lambdas capture their scalars by value: captured by reference, k_mid_resolve_each took 10 registers more.)
+template <class Col> struct Form { using col = Col; };
+template <int MAXNW, class F>
+TGSF_D auto by_length(int Q, F fn) {
+    if (Q <= 64) return fn(Form<Bv<1>>{});
+    if constexpr (MAXNW > 4) { if (Q > 256) return fn(Form<BvW>{}); }
+    if constexpr (MAXNW > 2) { if (Q > 192) return fn(Form<Bv<4>>{}); if (Q > 128) return fn(Form<Bv<3>>{}); }
+    return fn(Form<Bv<2>>{});
 }
-template <int MAXNW>
-TGSF_D int min_start_all_any(const DevParams& P, int a, const uint8_t* t, int T, int best) {
-    const int Q = P.Q[a];
-    if (Q <= 64) return min_start_all<1>(P, a, t, T, best);
-    if constexpr (MAXNW > 4) { if (Q > 256) return min_start_all_w(P, a, t, T, best); }
-    if constexpr (MAXNW > 2) { if (Q > 192) return min_start_all<4>(P, a, t, T, best); if (Q > 128) return min_start_all<3>(P, a, t, T, best); }
-    return min_start_all<2>(P, a, t, T, best);
-}
-template <int MAXNW>
-TGSF_D int start_of_any(const DevParams& P, int a, const uint8_t* t, int end, int best) {
-    const int Q = P.Q[a];
-    if (Q <= 64) return start_of<1>(P, a, t, end, best);
-    if constexpr (MAXNW > 4) { if (Q > 256) return start_of_w(P, a, t, end, best); }
-    if constexpr (MAXNW > 2) { if (Q > 192) return start_of<4>(P, a, t, end, best); if (Q > 128) return start_of<3>(P, a, t, end, best); }
-    return start_of<2>(P, a, t, end, best);
-}
-template <int MAXNW>
-TGSF_D int first_mlen_any(const DevParams& P, int a, const uint8_t* t, int s0, int e0, int best, int need, const LaneScratch& sc, bool exact) {
-    const int Q = P.Q[a];
-    if (Q <= 64) return first_mlen<1>(P, a, t, s0, e0, best, need, sc, exact);
-    if constexpr (MAXNW > 4) { if (Q > 256) return first_mlen_w(P, a, t, s0, e0, best, need, sc, exact); }
-    if constexpr (MAXNW > 2) { if (Q > 192) return first_mlen<4>(P, a, t, s0, e0, best, need, sc, exact); if (Q > 128) return first_mlen<3>(P, a, t, s0, e0, best, need, sc, exact); }
-    return first_mlen<2>(P, a, t, s0, e0, best, need, sc, exact);
-}
+
 
 // ---------------------------------------------------------------------------
 // k_end_windows: the 5' and 3' searches of GetEditDistance (src/TGSFilter.cpp:1266-1321).
@@ -1507,7 +1308,7 @@ TGSF_KERNEL k_end_windows(DevParams P, DevBatch B)
     const uint8_t* t = B.seq + B.off[r] + (e ? (L - W5) : 0);
     const LaneScratch sc = lane_scratch(B, 0);
     const int need = P.need_end[a];                        // mlen >= EndMatchLen && float(mlen)/Q >= EndSim (:1283-1288)
-    WinAln w = align_window_any<MAXNW>(P, a, t, W5, P.k_end[a], need, sc, false);
+    WinAln w = by_length<MAXNW>(P.Q[a], [=, &P](auto f) TGSF_INLINE_LAMBDA { return align_window<typename decltype(f)::col>(P, a, t, W5, P.k_end[a], need, sc, false); });
     if (w.best < 0) return;
     if (w.mlen < need) return;
     if (e == 0) {
@@ -1515,7 +1316,7 @@ TGSF_KERNEL k_end_windows(DevParams P, DevBatch B)
         atomicOr(&B.flags[r], (uint32_t)TGSF_RF_AD5P);
     } else {
         int mn = w.start0;
-        if (w.n > 1) mn = min_start_all_any<MAXNW>(P, a, t, W5, w.best);
+        if (w.n > 1) mn = by_length<MAXNW>(P.Q[a], [=, &P](auto f) TGSF_INLINE_LAMBDA { return min_start_all<typename decltype(f)::col>(P, a, t, W5, w.best); });
         B.clip3[(size_t)r * A + a] = L - W5 + mn;         // union of [L-W5+start_i, L)
         atomicOr(&B.flags[r], (uint32_t)TGSF_RF_AD3P);
     }
@@ -2129,15 +1930,22 @@ TGSF_KERNEL k_mid_recheck(DevParams P, DevBatch B, int a0, int na)
     for (uint32_t i = gtid(); i < n; i += gsize()) recheck_chunk(P, B, eq, a0, B.rc_list[i]);
 }
 
-// adapters of 65..256 bp: NW-word standard layout (NW = ceil(Q / 64) = 2, 3 or 4), one adapter per pass
-template <int NW>
+// adapters beyond 64 bp, one adapter per pass, over either form of the column: Bv<NW> (65..256 bp, NW = ceil(Q / 64) = 2, 3
+// or 4; the Eq rows in LDS, NW words a symbol) or BvW (beyond; the Eq rows read from the wide table in memory)
+template <class Col>
 TGSF_KERNEL k_mid_scanw(DevParams P, DevBatch B, int a)
 {
-    TGSF_SHARED uint64_t eqt[256][NW];
+    constexpr int RW = Col::kWide ? Col::kStride : Col::kWords;        // words a symbol of `rows`
+    const uint64_t* rows;
+    if constexpr (Col::kWide) rows = peq_fwd_of<Col>(P, a);
+    else {
+        TGSF_SHARED uint64_t eqt[256][RW];
+        for (uint32_t i = TGSF_COOP_BEGIN; i < 256u * RW; i += TGSF_COOP_STRIDE)
+            eqt[i / RW][i % RW] = P.peq_fwd[(size_t)a * 256 * kPeqW + (size_t)(i / RW) * kPeqW + (i % RW)];
+        TGSF_BLOCK_SYNC();
+        rows = &eqt[0][0];
+    }
     TGSF_SHARED int32_t tie_col[256][4];
-    for (uint32_t i = TGSF_COOP_BEGIN; i < 256u * NW; i += TGSF_COOP_STRIDE)
-        eqt[i / NW][i % NW] = P.peq_fwd[(size_t)a * 256 * kPeqW + (size_t)(i / NW) * kPeqW + (i % NW)];
-    TGSF_BLOCK_SYNC();
     const uint32_t total = B.seg_cnt[B.n];
     const uint32_t g = gtid();
     if (g >= total) return;
@@ -2155,7 +1963,7 @@ TGSF_KERNEL k_mid_scanw(DevParams P, DevBatch B, int a)
     const int c0 = blk * S > amid ? (int)(blk * S - amid) : 0;
     int c1 = (int)((blk + 1) * S - amid);
     if (c1 > ML) c1 = ML;
-    Bv<NW> s;
+    Col s;
     bv_init(s, Q);
     // As in k_mid_scan1: only the columns at the read's global minimum matter, so the lane keeps the columns tying ITS best
     // value (a 4-slot buffer, void as soon as a column does strictly better) and hands them over when the buffer fills or
@@ -2178,64 +1986,9 @@ TGSF_KERNEL k_mid_scanw(DevParams P, DevBatch B, int a)
     };
     int c = c0 - (Q + P.k_mid[a]);
     if (c < 0) c = 0;
-    for (; c < c0; c++) bv_step<NW>(s, eqt[mid[c]], 0, Q);
+    for (; c < c0; c++) bv_step(s, rows + (size_t)mid[c] * RW, 0, Q);   // warm-up columns
     for (; c < c1; c++) {
-        bv_step<NW>(s, eqt[mid[c]], 0, Q);
-        if (s.score < lim) { lim = s.score; ntie = 0; }
-        if (s.score == lim && lim <= top) {
-            if (ntie == 4) { hand_over(4); ntie = 0; }
-            ties[ntie++] = c;
-        }
-    }
-    if (ntie > 0) hand_over(ntie);
-    if (B.mid_mode == 1u && slot) B.seg_n[(size_t)g * P.n_adapters + a] = slot;
-}
-
-// adapters beyond 256 bp: the wide column (see BvW), one adapter per pass, Eq rows read from the wide table in memory
-TGSF_KERNEL k_mid_scan_wide(DevParams P, DevBatch B, int a)
-{
-    TGSF_SHARED int32_t tie_col[256][4];
-    const uint32_t total = B.seg_cnt[B.n];
-    const uint32_t g = gtid();
-    if (g >= total) return;
-    const uint32_t r = find_owner(B.seg_cnt, B.n, g);
-    const uint32_t seg = g - B.seg_cnt[r];
-    const int L = (int)B.len[r];
-    const int E = P.end_len;
-    const int ML = L - 2 * E;
-    const int Q = P.Q[a], nw = (Q + 63) >> 6;
-    if (ML < Q || P.k_mid[a] < 0) return;
-    const uint64_t* pf = P.peq_fwd_w + (size_t)a * 256 * kWideNW;
-    const uint8_t* mid = B.seq + B.off[r] + E;
-    const uint64_t S = (uint64_t)P.seg_cols;
-    const uint64_t amid = (uint64_t)(uintptr_t)mid;
-    const uint64_t blk = amid / S + seg;
-    const int c0 = blk * S > amid ? (int)(blk * S - amid) : 0;
-    int c1 = (int)((blk + 1) * S - amid);
-    if (c1 > ML) c1 = ML;
-    BvW s;
-    bvw_init(s, Q, nw);
-    int32_t* ties = tie_col[threadIdx.x];
-    int ntie = 0;
-    int lim = P.k_mid[a] + 1;
-    int top = P.k_mid[a];
-    if (B.mid_mode) {                                                  // after a pool overflow: see k_mid_scan1, k_mid_scanw
-        const int gmin = B.mid_best[(size_t)r * P.n_adapters + a];
-        if (gmin > P.k_mid[a]) return;
-        lim = gmin + 1;
-        top = gmin;
-    }
-    uint32_t slot = B.mid_mode == 2u ? B.seg_n[(size_t)g * P.n_adapters + a] : 0u;
-    auto hand_over = [&](int n) {
-        if (B.mid_mode == 1u) slot += (uint32_t)n;
-        else if (B.mid_mode == 2u) for (int i = 0; i < n; i++) place_candidate(B, slot++, ties[i], lim, a);
-        else if (worth_handing_over(B, r, a, P.n_adapters, lim)) for (int i = 0; i < n; i++) push_candidate(B, r, ties[i], lim, a);
-    };
-    int c = c0 - (Q + P.k_mid[a]);
-    if (c < 0) c = 0;
-    for (; c < c1; c++) {
-        bvw_step(s, pf + (size_t)mid[c] * kWideNW, 0, Q, nw, nullptr);
-        if (c < c0) continue;                                           // warm-up columns
+        bv_step(s, rows + (size_t)mid[c] * RW, 0, Q);
         if (s.score < lim) { lim = s.score; ntie = 0; }
         if (s.score == lim && lim <= top) {
             if (ntie == 4) { hand_over(4); ntie = 0; }
@@ -2275,8 +2028,8 @@ TGSF_KERNEL k_mid_resolve(DevParams P, DevBatch B)
     const uint8_t* win = B.seq + B.off[r] + E;
     const LaneScratch sc = lane_scratch(B, B.scratch_mid_wave0);
     const int need = P.need_mid[a];                                      // :1246, :1250-1252
-    const int s0 = start_of_any<MAXNW>(P, a, win, e0, best);
-    const int mlen = first_mlen_any<MAXNW>(P, a, win, s0, e0, best, need, sc, false);
+    const int s0 = by_length<MAXNW>(P.Q[a], [=, &P](auto f) TGSF_INLINE_LAMBDA { return start_of<typename decltype(f)::col>(P, a, win, e0, best); });
+    const int mlen = by_length<MAXNW>(P.Q[a], [=, &P](auto f) TGSF_INLINE_LAMBDA { return first_mlen<typename decltype(f)::col>(P, a, win, s0, e0, best, need, sc, false); });
     if (mlen < need) return;
     atomicOr(&B.flags[r], (uint32_t)TGSF_RF_ADMID);
     if (B.mid_mode) { B.mid_gate[idx] = 1u; return; }                  // the locations themselves: k_mid_resolve_each, a lane each
@@ -2284,7 +2037,7 @@ TGSF_KERNEL k_mid_resolve(DevParams P, DevBatch B)
         const int aux = B.pool[i].aux;
         if ((aux >> 16) != a || (aux & 0xFFFF) != best) continue;
         const int pos = B.pool[i].pos;
-        const int st = (pos == e0) ? s0 : start_of_any<MAXNW>(P, a, win, pos, best);
+        const int st = (pos == e0) ? s0 : by_length<MAXNW>(P.Q[a], [=, &P](auto f) TGSF_INLINE_LAMBDA { return start_of<typename decltype(f)::col>(P, a, win, pos, best); });
         int ts = st + E - P.extra_len, te = pos + E + 1 + P.extra_len;   // :1248-1256
         if (ts < 0) ts = 0;
         if (te > L) te = L;
@@ -2309,7 +2062,7 @@ TGSF_KERNEL k_mid_resolve_each(DevParams P, DevBatch B)
         if (!B.mid_gate[(size_t)r * A + a]) continue;
         const int L = (int)B.len[r], E = P.end_len;
         const uint8_t* win = B.seq + B.off[r] + E;
-        const int st = start_of_any<MAXNW>(P, a, win, pos, best);
+        const int st = by_length<MAXNW>(P.Q[a], [=, &P](auto f) TGSF_INLINE_LAMBDA { return start_of<typename decltype(f)::col>(P, a, win, pos, best); });
         int ts = st + E - P.extra_len, te = pos + E + 1 + P.extra_len;   // :1248-1256
         if (ts < 0) ts = 0;
         if (te > L) te = L;
@@ -3130,7 +2883,8 @@ TGSF_KERNEL k_align_windows(DevParams P, DevBatch B, const uint8_t* seq, const u
     if (k > Q) k = Q;                                    // edlib.cpp:565-567
     const LaneScratch sc = lane_scratch(B, 0);
     const uint8_t* t = seq + win_off[i];
-    WinAln w = align_window_any<MAXNW>(P, a, t, (int)win_len[i], k, 0, sc, true);
+    const int T = (int)win_len[i];
+    WinAln w = by_length<MAXNW>(Q, [=, &P](auto f) TGSF_INLINE_LAMBDA { return align_window<typename decltype(f)::col>(P, a, t, T, k, 0, sc, true); });
     res[i * 4 + 0] = w.best;
     res[i * 4 + 1] = w.best < 0 ? 0 : w.n;
     res[i * 4 + 2] = w.best < 0 ? 0 : w.mlen + w.best;

@@ -782,10 +782,10 @@ static void launch_scans(Run& r, uint32_t mode)
     Bm.mid_mode = mode;
     int a = 0;
     while (a < A) {
-        if (P.Q[a] > 256) { TGSF_LAUNCH(k_mid_scan_wide, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
-        if (P.Q[a] > 192) { TGSF_LAUNCH(k_mid_scanw<4>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
-        if (P.Q[a] > 128) { TGSF_LAUNCH(k_mid_scanw<3>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
-        if (P.Q[a] > 64) { TGSF_LAUNCH(k_mid_scanw<2>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
+        if (P.Q[a] > 256) { TGSF_LAUNCH(k_mid_scanw<BvW>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
+        if (P.Q[a] > 192) { TGSF_LAUNCH(k_mid_scanw<Bv<4>>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
+        if (P.Q[a] > 128) { TGSF_LAUNCH(k_mid_scanw<Bv<3>>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
+        if (P.Q[a] > 64) { TGSF_LAUNCH(k_mid_scanw<Bv<2>>, r.gseg, kBlock, ms, P, Bm, a); a++; continue; }
         // up to four adapters of one word class per pass: <= 32 bp (one dword per column; two a pass, below), 33..64 bp
         // (one qword), or -- the flat scan only -- 33..64 bp within few differences (the last 32 rows as a filter, the
         // rest rechecked)
