@@ -161,9 +161,11 @@ def _run(binary, td, sub, fin, flags, adapters, out_name="out.fq", to_stdout=Fal
 
 
 def compare_live(binary, ref_binary, reads, flags, adapters, fasta=False, in_fmt=None, out_name=None, to_stdout=False,
-                 raw_input=None, ranks=None, own_args=()):
+                 raw_input=None, ranks=None, own_args=(), ref_check=None):
     """Run the reference binary and ours on the same freshly written input: output file, INFO lines and the
-    report's table / data object must be identical.  in_fmt: fq | fq.gz | fa | bam | sam."""
+    report's table / data object must be identical.  in_fmt: fq | fq.gz | fa | bam | sam.
+    ref_check(returncode, stderr) is called on the reference's run before ours is looked at: a case asserts there that
+    the reference did what the case is built for (tests/prepass_domain.py)."""
     from tgsfilter_amd import synth
     in_fmt = in_fmt or ("fa" if fasta else "fq")
     out_name = out_name or ("out.fa" if in_fmt == "fa" else "out.fq")
@@ -190,6 +192,8 @@ def compare_live(binary, ref_binary, reads, flags, adapters, fasta=False, in_fmt
             synth.write_fastq(fin, reads)
         rc_r, out_r, err_r, html_r = _run(ref_binary, td, "ref", fin, flags, adapters, out_name, to_stdout)
         rc_o, out_o, err_o, html_o = _run(binary, td, "own", fin, flags, adapters, out_name, to_stdout, ranks=ranks, own_args=own_args)
+    if ref_check is not None:
+        ref_check(rc_r, err_r)
     if rc_r != 0:
         # parameter sets the reference itself cannot finish (e.g. nothing passes the filters: it dereferences an
         # empty vector, src/TGSFilter.cpp:3183): this side must refuse too, there is nothing else to compare

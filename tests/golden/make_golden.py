@@ -10,6 +10,7 @@ which compiles the reference from /root/reference where it lies).  The outputs a
   <case>.html.json     the <table> rows and the `var data = {...}` object of the HTML report
   <case>.cmd.json      the flags used
   edlib_vectors.json   kernel-level vectors from the reference's own edlib (HW/PATH)
+  prepass_<case>.*     the pre-pass cases (tests/prepass_domain.py): .in.fq.gz, .cmd.json and .stderr.txt only
 No reference source text is stored.
 """
 import ctypes as C
@@ -350,3 +351,10 @@ if __name__ == "__main__":
             run_case(name, *case)
     if not only or "edlib" in only:
         edlib_vectors()
+    # the pre-pass (tests/prepass_domain.py, GOLDENS): -A runs, which end before anything is filtered -- the input, the command
+    # and the reference's stderr, no output file and no report
+    from tests import prepass_domain
+    for name in prepass_domain.GOLDENS:
+        if not only or name in only:
+            err = prepass_domain.write_golden(name)
+            print(name, "\n    " + "\n    ".join(l for l in err.splitlines() if "adapter" in l))

@@ -594,6 +594,39 @@ def async_two_contexts(lib_path):
         c.close()
 
 
+def edlib_truth():
+    """truth(q, t, k) -> (distance, number of locations, alignment length, first start, first end, last end) of
+    edlibAlign(HW, PATH): edlib itself where oracle/_ref/libedlib_ref.so exists (compiled from the reference's
+    include/edlib.cpp), else the oracle's DP restatement.  Shared by align_windows_random and tests/prepass_domain.py."""
+    import ctypes as C
+    ref_so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libedlib_ref.so")
+    if os.path.exists(ref_so):
+        class Cfg(C.Structure):
+            _fields_ = [("k", C.c_int), ("mode", C.c_int), ("task", C.c_int), ("eq", C.c_void_p), ("neq", C.c_int)]
+
+        class Res(C.Structure):
+            _fields_ = [("status", C.c_int), ("editDistance", C.c_int), ("endLocations", C.POINTER(C.c_int)),
+                        ("startLocations", C.POINTER(C.c_int)), ("numLocations", C.c_int),
+                        ("alignment", C.POINTER(C.c_ubyte)), ("alignmentLength", C.c_int), ("alphabetLength", C.c_int)]
+        lib = C.CDLL(ref_so)
+        lib.edlibAlign.restype = Res
+        lib.edlibAlign.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, Cfg]
+        lib.edlibFreeAlignResult.argtypes = [Res]
+
+        def truth(q, t, k):
+            r = lib.edlibAlign(q, len(q), t, len(t), Cfg(k, 2, 2, None, 0))
+            n_ = r.numLocations
+            out = (r.editDistance, n_, r.alignmentLength, r.startLocations[0] if n_ else -1,
+                   r.endLocations[0] if n_ else -1, r.endLocations[n_ - 1] if n_ else -1)
+            lib.edlibFreeAlignResult(r)
+            return out
+    else:
+        def truth(q, t, k):
+            ed, n_, starts, ends_, alen = orc.align_hw(q, t, k)
+            return (ed, n_, alen, starts[0] if n_ else -1, ends_[0] if n_ else -1, ends_[-1] if n_ else -1)
+    return truth
+
+
 def align_windows_random(lib_path, n, seed=9, golden_dir=None, lengths=None, max_window=400, plant_whole=False,
                          adapters=None, alphabet=None, mutate=None):
     """tgsf_align_windows against edlib itself where oracle/_ref/libedlib_ref.so exists (compiled from the
@@ -602,8 +635,6 @@ def align_windows_random(lib_path, n, seed=9, golden_dir=None, lengths=None, max
     adapters: these instead (any bytes; one beyond 256 bp makes the context a wide one); alphabet: the bytes the windows
     are drawn from instead of ACGT; mutate: instead of synth.mutate (tests/bytes_domain.py: replacements from all 256
     values).  Without the three the cases are what they have always been."""
-    import ctypes as C
-    ref_so = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "libedlib_ref.so")
     rng = np.random.default_rng(seed)
     acgt = np.frombuffer(b"ACGT" if alphabet is None else bytes(alphabet), dtype=np.uint8)
     nsym = len(acgt)
@@ -652,30 +683,7 @@ def align_windows_random(lib_path, n, seed=9, golden_dir=None, lengths=None, max
         buf += t
     res, ends = ctx.align_windows(bytes(buf), off, ln, aid, ks)
     ctx.close()
-    if os.path.exists(ref_so):
-        class Cfg(C.Structure):
-            _fields_ = [("k", C.c_int), ("mode", C.c_int), ("task", C.c_int), ("eq", C.c_void_p), ("neq", C.c_int)]
-
-        class Res(C.Structure):
-            _fields_ = [("status", C.c_int), ("editDistance", C.c_int), ("endLocations", C.POINTER(C.c_int)),
-                        ("startLocations", C.POINTER(C.c_int)), ("numLocations", C.c_int),
-                        ("alignment", C.POINTER(C.c_ubyte)), ("alignmentLength", C.c_int), ("alphabetLength", C.c_int)]
-        lib = C.CDLL(ref_so)
-        lib.edlibAlign.restype = Res
-        lib.edlibAlign.argtypes = [C.c_char_p, C.c_int, C.c_char_p, C.c_int, Cfg]
-        lib.edlibFreeAlignResult.argtypes = [Res]
-
-        def truth(q, t, k):
-            r = lib.edlibAlign(q, len(q), t, len(t), Cfg(k, 2, 2, None, 0))
-            n_ = r.numLocations
-            out = (r.editDistance, n_, r.alignmentLength, r.startLocations[0] if n_ else -1,
-                   r.endLocations[0] if n_ else -1, r.endLocations[n_ - 1] if n_ else -1)
-            lib.edlibFreeAlignResult(r)
-            return out
-    else:
-        def truth(q, t, k):
-            ed, n_, starts, ends_, alen = orc.align_hw(q, t, k)
-            return (ed, n_, alen, starts[0] if n_ else -1, ends_[0] if n_ else -1, ends_[-1] if n_ else -1)
+    truth = edlib_truth()
     bad = []
     for i, (q, t, k) in enumerate(trip):
         got = (int(res[i, 0]), int(res[i, 1]), int(res[i, 2]), int(res[i, 3]), int(ends[i, 0]), int(ends[i, 1]))
