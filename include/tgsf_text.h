@@ -33,6 +33,9 @@
  * THE BAM INPUT SIDE (tgsf_text_bam_*, at the end, with its rule): inflated unaligned BAM records are decoded on the device
  * into the object's text buffer as FASTQ text, with the same index; from there everything above works unchanged.
  *
+ * THE BGZF INPUT SIDE (tgsf_text_bgzf_*, behind it, with its rule): BGZF members -- a .bam file or bgzip'ed FASTQ / FASTA as it is
+ * on disk -- are inflated on the device, a wave per member; tgsf_text_bgzf_bam_* are the BAM calls with the compressed bytes.
+ *
  * Conventions as in tgsf.h: plain C, 0 or a negative tgsf_status; calls on one object are serialised by the caller,
  * different objects may be driven from different threads.  No CPU fallback.
  */
@@ -239,7 +242,7 @@ int tgsf_text_out_stage_ms(tgsf_text* tx, float ms[3]);
  * ---- the BAM input side: inflated unaligned BAM records in, FASTQ text and its index out ------------------------------
  *
  * THE RULE.  Truth is decode_bam of the command line (tgsfilter_amd/host/bam.cpp, a restatement of the reference's sam_read1
- * loop).  The input is a chunk of INFLATED BAM bytes (BGZF inflation is the caller's) that begins at a record's block_size
+ * loop).  The input is a chunk of INFLATED BAM bytes (inflated by the caller, or by the BGZF input side) that begins at a record's block_size
  * field -- behind the BAM header (tgsf_text_bam_header) or at an earlier call's `consumed` -- and ends at any byte.
  *
  *   - The record at byte `at`: block_size is the little-endian u32 there, the record the block_size bytes behind it; it is
@@ -338,6 +341,146 @@ int tgsf_text_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint6
 int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
                          uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
                          tgsf_text_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out);
+
+/*
+ * ---- the BGZF input side: compressed members in, their inflated bytes out -----------------------------------------------
+ *
+ * THE RULE.  Truth is bgzf_peek / inflate_members of the command line (tgsfilter_amd/host/bam.cpp), with zlib as the arbiter
+ * of what a DEFLATE stream means.  The input is a chunk of the file's bytes as they are on disk that begins at a member --
+ * the start of the file or an earlier call's `consumed` -- and ends at any byte.
+ *
+ *   - A MEMBER at byte `at` starts with 1f 8b 08 04; xlen is the u16 at byte 10.  The extra field is walked as bgzf_peek walks
+ *     it: the subfield 'B','C' with slen == 2 gives bsize = u16 + 1, other subfields in front of it or behind it are stepped
+ *     over.  It is a member when 18 bytes are there, bsize >= 12 + xlen + 8 and at + bsize <= n_bytes.  payload = at + 12 + xlen,
+ *     clen = bsize - 12 - xlen - 8, usize is the u32 in the member's last four bytes.
+ *   - STRICTER THAN THE HOST: usize > 65536 is not BGZF and stops the walk as TGSF_TEXT_IRREGULAR.  That bounds everything the
+ *     device does for a member.
+ *   - The walk's stops: TGSF_TEXT_END -- nothing is left, or a non-final chunk ends inside a member or inside its header.
+ *     TGSF_TEXT_IRREGULAR -- the bytes at `consumed` are not a member, or the chunk is final and the bytes left are an
+ *     incomplete member.  TGSF_TEXT_CAPACITY -- max_blocks walked and bytes left, or the next member's usize does not fit
+ *     max_out_bytes.
+ *   - A member is GOOD iff usize == 0 and clen <= 2 (the EOF member: the host does not look at such a payload either), or
+ *     zlib's raw inflate of payload[0 .. clen) reaches the end of a final block having produced exactly usize bytes, without
+ *     consuming a bit at or behind 8 * clen.  Payload bytes behind the end of the final block are ignored, as by the host.
+ *     THE CRC32 IS NOT CHECKED, as by the host.  Everything zlib refuses makes the member BAD: a stored block whose NLEN is
+ *     not the complement of LEN; BTYPE 3; HLIT > 286 or HDIST > 30; a repeat code 16 with nothing before it or a repeat that
+ *     runs over HLIT + HDIST; no code for symbol 256; an over-subscribed code; an incomplete code other than a single code of
+ *     length 1; literal/length symbols 286 and 287, distance symbols 30 and 31, the unused code of an incomplete set; a
+ *     distance farther back than the bytes this member has produced; running out of input; a byte beyond usize, or ending
+ *     short of it.  (The repeats of the code lengths run across the literal/distance boundary: legal.  A distance alphabet
+ *     without any code is legal as long as no length symbol occurs.)
+ *   - The inflated bytes of member b are written at out + blocks[b].out, blocks[b].out being the sum of usize of the members
+ *     before it.  A BAD member writes nothing outside [out, out + usize) of its own range, and what it leaves inside is
+ *     unspecified; every other member's bytes are right.  bad_block is the LOWEST index of a bad member (UINT32_MAX: none).
+ *
+ * Members are found on the host (tgsf_text_bgzf_walk: headers and trailers only, O(members)); every bit of every payload is
+ * the device's, a wave per member.
+ */
+
+#define TGSF_TEXT_BGZF_MAX_CLEN 131072u   /* bytes of one member's DEFLATE stream the device form takes: the walk gives less than
+                                             65536; 65536 bytes in stored blocks of any size that a sane writer makes fit twice that */
+
+/* 24 bytes */
+typedef struct tgsf_text_bgzf_block {
+    uint64_t payload;      /* byte offset of the DEFLATE stream in the chunk                */
+    uint32_t clen;         /* its bytes                                                     */
+    uint32_t usize;        /* ISIZE: the inflated bytes, at most 65536                      */
+    uint64_t out;          /* sum of usize of the members before this one                   */
+} tgsf_text_bgzf_block;
+
+/* 40 bytes */
+typedef struct tgsf_text_bgzf_summary {
+    uint32_t n_blocks;
+    uint32_t stop;         /* TGSF_TEXT_*: the walk's                                                       */
+    uint64_t consumed;     /* compressed bytes: the offset of the first member that is not inflated         */
+    uint64_t out_bytes;    /* sum of usize over the members                                                 */
+    uint32_t bad_block;    /* the lowest bad member; UINT32_MAX: none                                       */
+    float    device_ms;    /* the inflate kernels by HIP events, when tgsf_text_profile is on and the call synchronises
+                              (tgsf_text_bgzf_inflate); else 0                                              */
+    uint64_t reserved;
+} tgsf_text_bgzf_summary;
+
+/* Host only: the member walk, as the rule above says.  blocks has room for max_blocks entries; *n of them are filled. */
+int tgsf_text_bgzf_walk(const uint8_t* gz, uint64_t n_bytes, int final, uint32_t max_blocks, uint64_t max_out_bytes,
+                        tgsf_text_bgzf_block* blocks, uint32_t* n, uint32_t* stop, uint64_t* consumed, uint64_t* out_bytes);
+
+/*
+ * Once, before the first inflate: the device buffer for chunks of up to max_gz_bytes compressed bytes (16-byte aligned,
+ * padded), the block table (max_blocks), the state and the summary.  No later call allocates.  An inflate before it is
+ * TGSF_E_INVALID, a second call is TGSF_E_INVALID, a chunk of n_bytes > max_gz_bytes or a table of n_blocks > max_blocks
+ * TGSF_E_CAPACITY before anything is copied.
+ */
+int tgsf_text_bgzf_reserve(tgsf_text* tx, uint64_t max_gz_bytes, uint32_t max_blocks);
+
+/*
+ * Compressed bytes in HOST memory: the walk (at most max_blocks members, at most min(out_capacity, max_bytes) inflated
+ * bytes), the bytes and the table go up, the members are inflated INTO THE OBJECT'S OWN TEXT BUFFER -- the call is capped by
+ * max_bytes and OVERWRITES THE TEXT AND INVALIDATES THE INDEX of the last call; in exchange bgzip'ed FASTQ / FASTA is ready for
+ * tgsf_text_index_device there (tgsf_text_buffers); a caller who wants neither uses the device form --, the summary and out_bytes bytes come down (out NULL:
+ * nothing but the summary comes down, and the room is max_bytes).  A walk that stops for
+ * TGSF_TEXT_CAPACITY before its first member (one member larger than the room) is TGSF_E_CAPACITY before anything is
+ * enqueued.  A bad member: TGSF_E_DATA naming it; the summary is filled, the other members' bytes have come down.
+ */
+int tgsf_text_bgzf_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint8_t* out, uint64_t out_capacity,
+                           tgsf_text_bgzf_summary* out_summary);
+
+/*
+ * The compressed bytes in HBM already (d_gz NULL: the object's buffer; a caller's must be 16-byte aligned and readable up to
+ * n_bytes rounded up to 16; bytes at and behind n_bytes never influence the result).  blocks[0 .. n_blocks) and walk_stop are
+ * the HOST results of tgsf_text_bgzf_walk on the same bytes; the table is checked against n_bytes and the rule's bounds
+ * (usize <= 65536, clen <= TGSF_TEXT_BGZF_MAX_CLEN, members in order, out the running sum: TGSF_E_INVALID), its last member's out + usize against out_capacity (TGSF_E_CAPACITY), both before anything is enqueued.
+ * d_out is any device pointer with out_capacity bytes -- the object's own text buffer for one (tgsf_text_buffers), to be
+ * followed by tgsf_text_index_device; d_summary NULL: the object's own.  Everything is enqueued on `hip_stream` (NULL: the
+ * object's own) and nothing is waited for.  The table and the state are the object's: one call at a time, or all on one stream.
+ */
+int tgsf_text_bgzf_inflate_device(tgsf_text* tx, const uint8_t* d_gz, uint64_t n_bytes, const tgsf_text_bgzf_block* blocks,
+                                  uint32_t n_blocks, uint32_t walk_stop, uint8_t* d_out, uint64_t out_capacity,
+                                  tgsf_text_bgzf_summary* d_summary, void* hip_stream);
+
+/*
+ * The chain walk of tgsf_text_bam_walk on BAM bytes that are in HBM (behind a device inflate the block_size chain is not on
+ * the host): one lane follows it, applying exactly that walk's rule to d_bam[start .. n_bytes) with the object's max_records;
+ * offsets count from d_bam (NULL: the object's BAM buffer).  Runs on the object's stream; n, stop, consumed and
+ * rec_off[0 .. n] (room for max_records + 1) come down in one copy and one wait.  tgsf_text_bam_decode_device takes the table
+ * as it is.  After tgsf_text_bam_reserve; start > n_bytes is TGSF_E_INVALID.
+ */
+int tgsf_text_bam_walk_device(tgsf_text* tx, const uint8_t* d_bam, uint64_t start, uint64_t n_bytes, int final, uint64_t* rec_off,
+                              uint32_t* n, uint32_t* stop, uint64_t* consumed);
+
+/*
+ * COMPRESSED BAM IN: tgsf_text_bam_decode / _submit / _filter with the bytes of the .bam file as they are on disk.  Members
+ * and records do not share boundaries, so a chunk is (gz bytes that begin at a member, skip): skip is the number of inflated
+ * bytes at the chunk's front that earlier calls consumed -- a BGZF virtual offset.  After tgsf_text_bam_reserve and
+ * tgsf_text_bgzf_reserve (and tgsf_text_out_reserve for the filter).
+ *   - The members are inflated into the object's BAM buffer: the walk's max_out_bytes is max_bam_bytes.  The record chunk is
+ *     inflated[skip .. gz.out_bytes); it is final only when `final` is set and every byte of the chunk was inflated
+ *     (gz.stop == TGSF_TEXT_END and gz.consumed == n_bytes).  skip > gz.out_bytes is TGSF_E_INVALID.
+ *   - bam.consumed counts inflated bytes from the chunk's first member.  (next_gz, next_skip) is where the next call begins:
+ *     the compressed offset, in this chunk, of the member that holds the first record not indexed, and that record's offset
+ *     in that member's inflated bytes; (gz.consumed, 0) when every inflated byte was consumed.
+ *   - NO PROGRESS IS NAMED: when gz.stop is TGSF_TEXT_CAPACITY (max_blocks or max_bam_bytes cut the members short) and the bytes
+ *     inflated hold no whole record from `skip` on, bam.stop is TGSF_TEXT_CAPACITY with n_records == 0 -- one record larger than
+ *     the object, as for inflated BAM -- and (next_gz, next_skip) is the pair the call was given: a caller must not loop on it.
+ *   - A bad member: TGSF_E_DATA naming it; the summaries are filled (gz), the decode and the filter have not run, the object
+ *     stays usable -- the contract of bad_qual, which holds here as it does for tgsf_text_bam_submit / _filter.
+ * The BAM header is the caller's, as for inflated BAM: inflate the first members (tgsf_text_bgzf_inflate), call
+ * tgsf_text_bam_header, and turn records_at into (member, skip) with the walk's table.
+ */
+typedef struct tgsf_text_bgzf_bam_summary {     /* 104 bytes */
+    tgsf_text_bgzf_summary gz;
+    tgsf_text_bam_summary bam;
+    uint64_t next_gz;
+    uint32_t next_skip;
+    uint32_t reserved;
+} tgsf_text_bgzf_bam_summary;
+
+int tgsf_text_bgzf_bam_decode(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final,
+                              const tgsf_text_index_arrays* out_index, tgsf_text_bgzf_bam_summary* out_summary);
+int tgsf_text_bgzf_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final,
+                              const tgsf_text_index_arrays* out_index, tgsf_text_bgzf_bam_summary* out_summary, tgsf_batch_out* batch_out);
+int tgsf_text_bgzf_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final, int fastq_out,
+                              uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                              tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out);
 
 #ifdef __cplusplus
 }

@@ -61,6 +61,17 @@ struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exa
     BamState* d_bstate = nullptr;
     tgsf_text_bam_summary* d_bsummary = nullptr;
     std::vector<uint64_t> h_rec_off;    // the walk of tgsf_text_bam_decode / _submit / _filter
+    uint64_t* d_bwalk = nullptr;        // tgsf_text_bam_walk_device: BamWalkHead (16 bytes), then max_records + 1 offsets
+    std::vector<uint64_t> h_bwalk;      // ... as they come down
+    // the BGZF input side (tgsf_text_bgzf_reserve): the chunk's compressed bytes, the members walked
+    bool gz_reserved = false;
+    uint64_t max_gz = 0;
+    uint32_t max_gblocks = 0;
+    uint8_t* d_gz = nullptr;            // max_gz rounded up to 16, + TGSF_TEXT_PAD
+    tgsf_text_bgzf_block* d_gblocks = nullptr;
+    BgzfState* d_gstate = nullptr;
+    tgsf_text_bgzf_summary* d_gsummary = nullptr;
+    std::vector<tgsf_text_bgzf_block> h_gblocks;   // the walk of tgsf_text_bgzf_inflate
     // around the last index, and around the stages of the last format (profile)
     rt_event ev[2] = {nullptr, nullptr};
     bool ev_recorded = false;
@@ -560,8 +571,10 @@ extern "C" int tgsf_text_bam_reserve(tgsf_text* tx, uint64_t max_bam_bytes)
     if (!e) e |= dev_alloc(tx, &tx->d_boseq, m);
     if (!e) e |= dev_alloc(tx, &tx->d_bstate, 1);
     if (!e) e |= dev_alloc(tx, &tx->d_bsummary, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_bwalk, m + 3);
     if (e) return fail(tx, TGSF_E_HIP, "device allocation failed (%llu bytes of BAM, %u records)", (unsigned long long)max_bam_bytes, tx->max_records);
     tx->h_rec_off.resize(m + 1);
+    tx->h_bwalk.resize(m + 3);
     tx->max_bam = max_bam_bytes;
     tx->bam_reserved = true;
     return TGSF_OK;
@@ -625,6 +638,41 @@ extern "C" int tgsf_text_bam_decode_device(tgsf_text* tx, const uint8_t* d_bam, 
                        d_summary ? d_summary : tx->d_bsummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
 }
 
+// the chain walk on the device, on the object's stream; one copy and one wait bring n, stop, consumed and the offsets down
+static int bam_walk_down(tgsf_text* tx, const uint8_t* d_bam, uint64_t start, uint64_t n_bytes, int final, uint64_t* rec_off, uint32_t* n,
+                         uint32_t* stop, uint64_t* consumed)
+{
+    static_assert(sizeof(BamWalkHead) == 16, "the head is two of the table's words");
+    TGSF_LAUNCH_COOP(k_bam_walk, 1, 64, tx->stream, d_bam, start, n_bytes, final, tx->max_records, (BamWalkHead*)tx->d_bwalk, tx->d_bwalk + 2);
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+    // a walked record has 36 bytes or more: the head and as many offsets as the bytes can hold records, and one
+    const uint64_t most = std::min<uint64_t>(tx->max_records, (n_bytes - start) / 36u);
+    int he = rt_d2h(tx->h_bwalk.data(), tx->d_bwalk, (size_t)(2 + most + 1) * 8, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    BamWalkHead head;
+    memcpy(&head, tx->h_bwalk.data(), sizeof head);
+    memcpy(rec_off, tx->h_bwalk.data() + 2, ((size_t)head.n + 1) * 8);
+    *n = head.n;
+    *stop = head.stop;
+    *consumed = head.consumed;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bam_walk_device(tgsf_text* tx, const uint8_t* d_bam, uint64_t start, uint64_t n_bytes, int final, uint64_t* rec_off,
+                                         uint32_t* n, uint32_t* stop, uint64_t* consumed)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!rec_off || !n || !stop || !consumed) return fail(tx, TGSF_E_INVALID, "null argument");
+    if (!tx->bam_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bam_reserve has not been called on this object: no table to walk into");
+    if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
+    if (start > n_bytes) return fail(tx, TGSF_E_INVALID, "the walk starts at byte %llu of %llu", (unsigned long long)start, (unsigned long long)n_bytes);
+    if (!d_bam && n_bytes > tx->max_bam)
+        return fail(tx, TGSF_E_CAPACITY, "BAM chunk of %llu bytes, the object was reserved for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_bam);
+    (void)rt_set_device(tx->device);
+    return bam_walk_down(tx, d_bam ? d_bam : tx->d_bam, start, n_bytes, final, rec_off, n, stop, consumed);
+}
+
 // walk, upload, decode on the object's stream; the summary comes down (the one wait)
 static int bam_decode_down(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, tgsf_text_bam_summary* sum)
 {
@@ -658,9 +706,10 @@ extern "C" int tgsf_text_bam_decode(tgsf_text* tx, const uint8_t* bam, uint64_t 
 }
 
 // the host refuses the whole input for a quality that decodes to '\n'; here the call, naming the record as the host does
-static int bad_quality(tgsf_text* tx, const uint8_t* bam, const tgsf_text_bam_summary& sum)
+// (rec: the record's block_size field and what follows it, as far as the name reaches)
+static int bad_quality(tgsf_text* tx, const uint8_t* rec, const tgsf_text_bam_summary& sum)
 {
-    const uint8_t* r = bam + tx->h_rec_off[sum.bad_qual] + 4;
+    const uint8_t* r = rec + 4;
     const char* name = reinterpret_cast<const char*>(r + 32);
     return fail(tx, TGSF_E_DATA, "unsupported quality value in %.*s (record %u of the chunk): the filter has not run", (int)strnlen(name, r[8]), name, sum.bad_qual);
 }
@@ -669,13 +718,18 @@ static int bad_quality(tgsf_text* tx, const uint8_t* bam, const tgsf_text_bam_su
 // How the chunk gets into the object and where its summary goes.  Text (text_summary): upload and index; the caller's summary
 // is written when the call has succeeded.  BAM (bam_summary): walk, copy up, decode; the text has text_bytes bytes, the
 // caller's summary is written before the filter runs, and a quality that decodes to '\n' refuses the chunk.
+// Compressed BAM (gz_summary, with bam_summary = &gz_summary->bam): the members inflated into the object's BAM buffer, the
+// chain walked there from byte `skip` on, then the decode as for BAM.
 struct Ingest {
     const uint8_t* bytes;
     uint64_t n_bytes;
     int fasta, final;
     tgsf_text_summary* text_summary;
     tgsf_text_bam_summary* bam_summary;
+    tgsf_text_bgzf_bam_summary* gz_summary;
+    uint32_t skip;
 };
+static int bgzf_bam_decode_down(tgsf_text* tx, const Ingest& in, tgsf_text_bam_summary* bs);
 // where tgsf_text_filter and tgsf_text_bam_filter have the kept records formatted to
 struct FormatTo {
     int fastq_out;
@@ -700,7 +754,7 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
     tgsf_text_summary ts;
     tgsf_text_bam_summary bs;
     if (in.bam_summary) {
-        if ((e = bam_decode_down(tx, in.bytes, in.n_bytes, in.final, &bs))) return e;
+        if ((e = in.gz_summary ? bgzf_bam_decode_down(tx, in, &bs) : bam_decode_down(tx, in.bytes, in.n_bytes, in.final, &bs))) return e;
         *in.bam_summary = bs;
     } else {
         if ((e = upload(tx, in.bytes, in.n_bytes))) return e;
@@ -709,7 +763,15 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
     }
     const uint32_t n_records = in.bam_summary ? bs.n_records : ts.n_records;
     if (bo) bo->n_frags = 0;
-    if (in.bam_summary && bs.bad_qual != 0xFFFFFFFFu) return bad_quality(tx, in.bytes, bs);
+    if (in.bam_summary && bs.bad_qual != 0xFFFFFFFFu) {
+        if (!in.gz_summary) return bad_quality(tx, in.bytes + tx->h_rec_off[bs.bad_qual], bs);
+        uint8_t rec[4 + 32 + 255] = {0};                               // the record's name is in HBM only
+        const uint64_t at = tx->h_rec_off[bs.bad_qual];
+        int he = rt_d2h(rec, tx->d_bam + at, (size_t)std::min<uint64_t>(sizeof rec, in.gz_summary->gz.out_bytes - at), tx->stream);
+        if (!he) he = rt_sync(tx->stream);
+        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+        return bad_quality(tx, rec, bs);
+    }
     uint32_t nf = 0;
     if ((e = run_filter(tx, ctx, n_records, in.bam_summary ? bs.text_bytes : in.n_bytes, bo, d_fr, fr_cap, &nf))) return e;
     if ((e = fetch_index(tx, out_index, n_records))) return e;
@@ -764,4 +826,250 @@ extern "C" int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t*
     if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
     return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
+}
+
+// ---- the BGZF input side ---------------------------------------------------------------------------------------------------
+static uint32_t gz_le16(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8; }
+
+extern "C" int tgsf_text_bgzf_walk(const uint8_t* gz, uint64_t n_bytes, int final, uint32_t max_blocks, uint64_t max_out_bytes,
+                                   tgsf_text_bgzf_block* blocks, uint32_t* n, uint32_t* stop, uint64_t* consumed, uint64_t* out_bytes)
+{
+    if (!n || !stop || !consumed || !out_bytes || (!blocks && max_blocks) || (!gz && n_bytes)) return fail(nullptr, TGSF_E_INVALID, "null argument");
+    if (final != 0 && final != 1) return fail(nullptr, TGSF_E_INVALID, "final is 0 or 1");
+    uint64_t at = 0, out = 0;
+    uint32_t k = 0, why = TGSF_TEXT_END;
+    const uint32_t cut = final ? TGSF_TEXT_IRREGULAR : TGSF_TEXT_END;  // the bytes left are the front of a member, as far as they go
+    while (at < n_bytes) {
+        const uint8_t* p = gz + at;
+        const uint64_t left = n_bytes - at;
+        const uint8_t magic[4] = {0x1f, 0x8b, 8, 4};
+        if (memcmp(p, magic, (size_t)std::min<uint64_t>(left, 4)) != 0) { why = TGSF_TEXT_IRREGULAR; break; }
+        if (left < 18) { why = cut; break; }
+        const uint64_t xlen = gz_le16(p + 10);
+        if (left < 12 + xlen) { why = cut; break; }
+        uint64_t bsize = 0;
+        for (uint64_t x = 12; x + 4 <= 12 + xlen;) {                   // bgzf_peek's walk of the extra field
+            const uint64_t slen = gz_le16(p + x + 2);
+            if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen) bsize = (uint64_t)gz_le16(p + x + 4) + 1;
+            x += 4 + slen;
+        }
+        if (bsize < 12 + xlen + 8) { why = TGSF_TEXT_IRREGULAR; break; }
+        if (bsize > left) { why = cut; break; }
+        const uint32_t usize = bam_le32(p + bsize - 4);
+        if (usize > 65536u) { why = TGSF_TEXT_IRREGULAR; break; }
+        if (k == max_blocks || usize > max_out_bytes - out) { why = TGSF_TEXT_CAPACITY; break; }
+        blocks[k].payload = at + 12 + xlen;
+        blocks[k].clen = (uint32_t)(bsize - 12 - xlen - 8);
+        blocks[k].usize = usize;
+        blocks[k].out = out;
+        out += usize;
+        at += bsize;
+        k++;
+    }
+    *n = k;
+    *stop = why;
+    *consumed = at;
+    *out_bytes = out;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bgzf_reserve(tgsf_text* tx, uint64_t max_gz_bytes, uint32_t max_blocks)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (tx->gz_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bgzf_reserve has been called already (%llu bytes, %u members)", (unsigned long long)tx->max_gz, tx->max_gblocks);
+    if (max_gz_bytes == 0 || max_blocks == 0) return fail(tx, TGSF_E_INVALID, "max_gz_bytes and max_blocks must be positive");
+    (void)rt_set_device(tx->device);
+    int e = 0;
+    e |= dev_alloc(tx, &tx->d_gz, ((max_gz_bytes + 15u) & ~15ull) + TGSF_TEXT_PAD);
+    if (!e) e |= dev_alloc(tx, &tx->d_gblocks, max_blocks);
+    if (!e) e |= dev_alloc(tx, &tx->d_gstate, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_gsummary, 1);
+    if (e) return fail(tx, TGSF_E_HIP, "device allocation failed (%llu compressed bytes, %u members)", (unsigned long long)max_gz_bytes, max_blocks);
+    tx->h_gblocks.resize(max_blocks);
+    tx->max_gz = max_gz_bytes;
+    tx->max_gblocks = max_blocks;
+    tx->gz_reserved = true;
+    return TGSF_OK;
+}
+
+// what every inflate is refused for before anything is copied or enqueued
+static int check_bgzf(tgsf_text* tx, uint64_t n_bytes)
+{
+    if (!tx->gz_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bgzf_reserve has not been called on this object: no buffers to inflate with");
+    if (n_bytes > tx->max_gz)
+        return fail(tx, TGSF_E_CAPACITY, "BGZF chunk of %llu bytes, the object was reserved for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_gz);
+    return TGSF_OK;
+}
+
+// the table up and the launches of one inflate, on st; nothing is waited for.  The table has been checked.
+static int enqueue_bgzf(tgsf_text* tx, const uint8_t* d_gz, const tgsf_text_bgzf_block* blocks, uint32_t n_blocks, uint32_t walk_stop,
+                        uint64_t consumed, uint64_t out_bytes, uint8_t* d_out, tgsf_text_bgzf_summary* d_summary, rt_stream st)
+{
+    int he = n_blocks ? rt_h2d(tx->d_gblocks, blocks, (size_t)n_blocks * sizeof *blocks, st) : 0;
+    if (!he) he = rt_memset(tx->d_gstate, 0xFF, sizeof(BgzfState), st);
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    // a wave per member, at most a few per SIMD of the device: they stride
+    const unsigned g = grid_cap(std::min(std::max(blocks_for((uint64_t)n_blocks * kTextLanes, kTextThreads), 1u), 2048u));
+    if (tx->profile) (void)rt_event_record(tx->ev[0], st);
+    if (n_blocks) TGSF_LAUNCH(k_bgzf_inflate, g, kTextThreads, st, d_gz, (const tgsf_text_bgzf_block*)tx->d_gblocks, n_blocks, d_out, tx->d_gstate);
+    TGSF_LAUNCH_COOP(k_bgzf_finish, 1, 64, st, n_blocks, walk_stop, consumed, out_bytes, (const BgzfState*)tx->d_gstate, d_summary);
+    if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bgzf_inflate_device(tgsf_text* tx, const uint8_t* d_gz, uint64_t n_bytes, const tgsf_text_bgzf_block* blocks,
+                                             uint32_t n_blocks, uint32_t walk_stop, uint8_t* d_out, uint64_t out_capacity,
+                                             tgsf_text_bgzf_summary* d_summary, void* hip_stream)
+{
+    if (!tx) return TGSF_E_INVALID;
+    int e = check_bgzf(tx, n_bytes);
+    if (e) return e;
+    if ((!blocks && n_blocks) || (!d_out && n_blocks)) return fail(tx, TGSF_E_INVALID, "null argument: the block table of tgsf_text_bgzf_walk, or the output");
+    if (walk_stop > TGSF_TEXT_CAPACITY) return fail(tx, TGSF_E_INVALID, "walk_stop is one of TGSF_TEXT_END, _IRREGULAR, _CAPACITY");
+    if (n_blocks > tx->max_gblocks) return fail(tx, TGSF_E_CAPACITY, "%u members, the object was reserved for %u", n_blocks, tx->max_gblocks);
+    if (!d_gz) d_gz = tx->d_gz;
+    if ((uintptr_t)d_gz & 15u) return fail(tx, TGSF_E_INVALID, "the compressed bytes on the device must be 16-byte aligned");
+    uint64_t out = 0, end = 0;
+    for (uint32_t b = 0; b < n_blocks; b++) {                          // the kernel's bounds are these words
+        const tgsf_text_bgzf_block& k = blocks[b];
+        if (k.payload < end || k.payload > n_bytes || k.clen > n_bytes - k.payload || k.clen > TGSF_TEXT_BGZF_MAX_CLEN || k.usize > 65536u || k.out != out)
+            return fail(tx, TGSF_E_INVALID, "member %u of the block table is not what tgsf_text_bgzf_walk gives for a chunk of %llu bytes", b, (unsigned long long)n_bytes);
+        end = k.payload + k.clen;
+        out += k.usize;
+    }
+    if (out > out_capacity) return fail(tx, TGSF_E_CAPACITY, "the members inflate to %llu bytes, there is room for %llu", (unsigned long long)out, (unsigned long long)out_capacity);
+    (void)rt_set_device(tx->device);
+    return enqueue_bgzf(tx, d_gz, blocks, n_blocks, walk_stop, n_blocks ? end + 8 : 0, out, d_out, d_summary ? d_summary : tx->d_gsummary,
+                        hip_stream ? (rt_stream)hip_stream : tx->stream);
+}
+
+extern "C" int tgsf_text_bgzf_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint8_t* out, uint64_t out_capacity,
+                                      tgsf_text_bgzf_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!out_summary || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
+    int e = check_bgzf(tx, n_bytes);
+    if (e) return e;
+    const uint64_t room = out ? std::min(out_capacity, tx->max_bytes) : tx->max_bytes;
+    uint32_t n = 0, walk_stop = 0;
+    uint64_t consumed = 0, out_bytes = 0;
+    e = tgsf_text_bgzf_walk(gz, n_bytes, final, tx->max_gblocks, room, tx->h_gblocks.data(), &n, &walk_stop, &consumed, &out_bytes);
+    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
+    if (!n && walk_stop == TGSF_TEXT_CAPACITY)
+        return fail(tx, TGSF_E_CAPACITY, "the first member does not fit: room for %llu bytes (out_capacity %llu, the text buffer %llu)",
+                    (unsigned long long)room, (unsigned long long)out_capacity, (unsigned long long)tx->max_bytes);
+    (void)rt_set_device(tx->device);
+    int he = consumed ? rt_h2d(tx->d_gz, gz, consumed, tx->stream) : 0;
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    if ((e = enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), n, walk_stop, consumed, out_bytes, tx->d_text, tx->d_gsummary, tx->stream))) return e;
+    tgsf_text_bgzf_summary sum;
+    he = rt_d2h(&sum, tx->d_gsummary, sizeof sum, tx->stream);
+    if (!he && out && out_bytes) he = rt_d2h(out, tx->d_text, out_bytes, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    sum.device_ms = index_ms(tx);
+    *out_summary = sum;
+    if (sum.bad_block != 0xFFFFFFFFu)
+        return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes", sum.bad_block,
+                    (unsigned long long)tx->h_gblocks[sum.bad_block].payload, tx->h_gblocks[sum.bad_block].usize);
+    return TGSF_OK;
+}
+
+// ---- compressed BAM in: the one-call forms, resumed by a BGZF virtual offset ---------------------------------------------------
+// walk, upload, inflate into the BAM buffer (the first wait: a bad member ends the call), the chain walk on the device (the
+// second), the decode (the third: the record count).  *in.gz_summary is filled as far as the call gets.
+static int bgzf_bam_decode_down(tgsf_text* tx, const Ingest& in, tgsf_text_bam_summary* bs)
+{
+    tgsf_text_bgzf_bam_summary* S = in.gz_summary;
+    memset(S, 0, sizeof *S);
+    S->gz.bad_block = S->bam.bad_qual = 0xFFFFFFFFu;
+    uint32_t n = 0, gz_stop = 0;
+    uint64_t consumed = 0, out_bytes = 0;
+    int e = tgsf_text_bgzf_walk(in.bytes, in.n_bytes, in.final, tx->max_gblocks, tx->max_bam, tx->h_gblocks.data(), &n, &gz_stop, &consumed, &out_bytes);
+    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
+    S->gz.n_blocks = n; S->gz.stop = gz_stop; S->gz.consumed = consumed; S->gz.out_bytes = out_bytes;
+    if (in.skip > out_bytes)
+        return fail(tx, TGSF_E_INVALID, "skip is %u, the %u members of the chunk inflate to %llu bytes", in.skip, n, (unsigned long long)out_bytes);
+    int he = consumed ? rt_h2d(tx->d_gz, in.bytes, consumed, tx->stream) : 0;
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    if ((e = enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), n, gz_stop, consumed, out_bytes, tx->d_bam, tx->d_gsummary, tx->stream))) return e;
+    he = rt_d2h(&S->gz, tx->d_gsummary, sizeof S->gz, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    S->gz.device_ms = index_ms(tx);
+    if (S->gz.bad_block != 0xFFFFFFFFu)
+        return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes: nothing was decoded", S->gz.bad_block,
+                    (unsigned long long)tx->h_gblocks[S->gz.bad_block].payload, tx->h_gblocks[S->gz.bad_block].usize);
+    // the records are final only when the file ends here and every byte of the chunk was inflated
+    const int rec_final = in.final && gz_stop == TGSF_TEXT_END && consumed == in.n_bytes;
+    uint32_t n_walked = 0, walk_stop = 0;
+    uint64_t walked_to = 0;
+    if ((e = bam_walk_down(tx, tx->d_bam, in.skip, out_bytes, rec_final, tx->h_rec_off.data(), &n_walked, &walk_stop, &walked_to))) return e;
+    if ((e = enqueue_bam(tx, tx->d_bam, tx->h_rec_off.data(), n_walked, walk_stop, tx->d_index, tx->d_bsummary, tx->stream))) return e;
+    he = rt_d2h(bs, tx->d_bsummary, sizeof *bs, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    bs->device_ms = index_ms(tx);
+    S->bam = *bs;
+    // the virtual offset of the first record that is not indexed: the last member that begins at or in front of it holds it
+    S->next_gz = consumed;
+    S->next_skip = 0;
+    if (bs->consumed < out_bytes) {
+        uint32_t lo = 0, hi = n;                                       // the first member that begins behind it
+        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (tx->h_gblocks[mid].out > bs->consumed) hi = mid; else lo = mid + 1; }
+        const uint32_t m = lo - 1;
+        S->next_gz = m ? tx->h_gblocks[m - 1].payload + tx->h_gblocks[m - 1].clen + 8 : 0;
+        S->next_skip = (uint32_t)(bs->consumed - tx->h_gblocks[m].out);
+    }
+    // the members of this call were cut short by the object's room and hold no whole record, and the next call would be this
+    // one again: named as what it is, a record larger than the object, instead of a chunk to be continued
+    if (gz_stop == TGSF_TEXT_CAPACITY && bs->n_records == 0 && bs->stop == TGSF_TEXT_END && S->next_gz == 0 && S->next_skip == in.skip)
+        bs->stop = S->bam.stop = TGSF_TEXT_CAPACITY;
+    return TGSF_OK;
+}
+
+// what the three calls are refused for before anything is copied or enqueued
+static int check_bgzf_bam(tgsf_text* tx, uint64_t n_bytes, int final)
+{
+    if (!tx->bam_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bam_reserve has not been called on this object: no buffer to inflate into");
+    if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
+    return check_bgzf(tx, n_bytes);
+}
+
+extern "C" int tgsf_text_bgzf_bam_decode(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final,
+                                         const tgsf_text_index_arrays* out_index, tgsf_text_bgzf_bam_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!out_summary || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_bgzf_bam(tx, n_bytes, final);
+    if (e) return e;
+    (void)rt_set_device(tx->device);
+    tgsf_text_bam_summary bs;
+    if ((e = bgzf_bam_decode_down(tx, {gz, n_bytes, 0, final, nullptr, &out_summary->bam, out_summary, skip}, &bs))) return e;
+    return fetch_index(tx, out_index, bs.n_records);
+}
+
+extern "C" int tgsf_text_bgzf_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final,
+                                         const tgsf_text_index_arrays* out_index, tgsf_text_bgzf_bam_summary* out_summary, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !bo || !bo->reads || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    const int e = check_bgzf_bam(tx, n_bytes, final);
+    if (e) return e;
+    return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &out_summary->bam, out_summary, skip}, out_index, bo, nullptr);
+}
+
+extern "C" int tgsf_text_bgzf_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final, int fastq_out,
+                                         uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
+                                         tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!gz && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, 0, fastq_out);
+    if (!e) e = check_bgzf_bam(tx, n_bytes, final);
+    if (e) return e;
+    const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
+    return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &in_summary->bam, in_summary, skip}, out_index, bo, &to);
 }

@@ -8,6 +8,10 @@
     tx.reserve_bam(max_bam_bytes)                       # once; then, for inflated unaligned BAM from bam_header()'s offset on,
     idx, bam_summary = tx.bam_decode(bam)               # the records as FASTQ text in the object, and its index
     clean, rec_end, out_summary, bam_summary = tx.bam_filter(ctx, bam)   # BAM in, clean text out
+    tx.reserve_bgzf(max_gz_bytes, max_blocks)           # once; then BGZF members as they are on disk:
+    data, gz_summary = tx.inflate(gz)                   # inflated on the device (bgzip'ed FASTQ / FASTA lands in the text buffer)
+    at, skip = tx.bgzf_bam_start(gz)                    # where a .bam file's records begin, as a BGZF virtual offset
+    clean, rec_end, out_summary, s = tx.bgzf_bam_filter(ctx, gz[at:], skip)   # compressed BAM in, clean text out; s["next_gz"], s["next_skip"] resume
 
 There is no CPU fallback: the library found beside this file must be the HIP build.  (tests/emul builds a serial
 emulation of the same kernels; only tests pass its path in.)
@@ -38,6 +42,8 @@ SYMBOLS = [
     "tgsf_text_out_reserve", "tgsf_text_format_device", "tgsf_text_format", "tgsf_text_filter", "tgsf_text_out_stage_ms",
     "tgsf_text_bam_header", "tgsf_text_bam_walk", "tgsf_text_bam_reserve", "tgsf_text_bam_decode", "tgsf_text_bam_decode_device",
     "tgsf_text_bam_submit", "tgsf_text_bam_filter",
+    "tgsf_text_bgzf_walk", "tgsf_text_bgzf_reserve", "tgsf_text_bgzf_inflate", "tgsf_text_bgzf_inflate_device",
+    "tgsf_text_bam_walk_device", "tgsf_text_bgzf_bam_decode", "tgsf_text_bgzf_bam_submit", "tgsf_text_bgzf_bam_filter",
 ]
 
 
@@ -76,7 +82,37 @@ class BamSummary(C.Structure):
                 "longest": self.longest, "bad_qual": self.bad_qual, "device_ms": self.device_ms, "reserved": self.reserved}
 
 
-NO_BAD_QUAL = 0xFFFFFFFF
+class BgzfBlock(C.Structure):
+    _fields_ = [("payload", C.c_uint64), ("clen", C.c_uint32), ("usize", C.c_uint32), ("out", C.c_uint64)]
+
+
+BGZF_BLOCK_DTYPE = np.dtype([("payload", "<u8"), ("clen", "<u4"), ("usize", "<u4"), ("out", "<u8")])
+
+
+class BgzfSummary(C.Structure):
+    _fields_ = [("n_blocks", C.c_uint32), ("stop", C.c_uint32), ("consumed", C.c_uint64), ("out_bytes", C.c_uint64),
+                ("bad_block", C.c_uint32), ("device_ms", C.c_float), ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        return {"n_blocks": self.n_blocks, "stop": self.stop, "consumed": self.consumed, "out_bytes": self.out_bytes,
+                "bad_block": self.bad_block, "device_ms": self.device_ms, "reserved": self.reserved}
+
+
+class BgzfBamSummary(C.Structure):
+    _fields_ = [("gz", BgzfSummary), ("bam", BamSummary), ("next_gz", C.c_uint64), ("next_skip", C.c_uint32), ("reserved", C.c_uint32)]
+
+    @property
+    def n_records(self):
+        return self.bam.n_records
+
+    def as_dict(self):
+        return {"gz": self.gz.as_dict(), "bam": self.bam.as_dict(), "next_gz": self.next_gz, "next_skip": self.next_skip, "reserved": self.reserved}
+
+
+NO_BAD_QUAL = NO_BAD_BLOCK = 0xFFFFFFFF
+assert C.sizeof(BgzfBamSummary) == 104
+assert C.sizeof(BgzfBlock) == 24 == BGZF_BLOCK_DTYPE.itemsize
+assert C.sizeof(BgzfSummary) == 40
 assert C.sizeof(Summary) == 32
 assert C.sizeof(BamSummary) == 48
 assert C.sizeof(OutSummary) == 32
@@ -123,6 +159,15 @@ def load(path: str | None = None):
         L.tgsf_text_bam_submit.argtypes = [vp, vp, vp, u64, i, C.POINTER(IndexArrays), C.POINTER(BamSummary), C.POINTER(abi.BatchOut)]
         L.tgsf_text_bam_filter.argtypes = [vp, vp, vp, u64, i, i, vp, u64, vp, C.POINTER(OutSummary), C.POINTER(BamSummary),
                                            C.POINTER(IndexArrays), C.POINTER(abi.BatchOut)]
+        L.tgsf_text_bgzf_walk.argtypes = [vp, u64, i, u32, u64, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64), C.POINTER(u64)]
+        L.tgsf_text_bgzf_reserve.argtypes = [vp, u64, u32]
+        L.tgsf_text_bgzf_inflate.argtypes = [vp, vp, u64, i, vp, u64, C.POINTER(BgzfSummary)]
+        L.tgsf_text_bgzf_inflate_device.argtypes = [vp, vp, u64, vp, u32, u32, vp, u64, vp, vp]
+        L.tgsf_text_bam_walk_device.argtypes = [vp, vp, u64, u64, i, vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u64)]
+        L.tgsf_text_bgzf_bam_decode.argtypes = [vp, vp, u64, u32, i, C.POINTER(IndexArrays), C.POINTER(BgzfBamSummary)]
+        L.tgsf_text_bgzf_bam_submit.argtypes = [vp, vp, vp, u64, u32, i, C.POINTER(IndexArrays), C.POINTER(BgzfBamSummary), C.POINTER(abi.BatchOut)]
+        L.tgsf_text_bgzf_bam_filter.argtypes = [vp, vp, vp, u64, u32, i, i, vp, u64, vp, C.POINTER(OutSummary), C.POINTER(BgzfBamSummary),
+                                                C.POINTER(IndexArrays), C.POINTER(abi.BatchOut)]
         if L.tgsf_text_abi_version() != ABI_VERSION:
             raise RuntimeError("libtgsf_text ABI version mismatch")
         _LIBS[path] = L
@@ -162,11 +207,25 @@ def bam_walk(bam, max_records: int, final=True, lib_path: str | None = None):
     return rec_off[:n.value + 1].copy(), stop.value, consumed.value
 
 
+def bgzf_walk(gz, max_blocks: int, max_out_bytes: int = (1 << 64) - 1, final=True, lib_path: str | None = None):
+    """The member walk on the host for a chunk that begins at a BGZF member: (blocks as BGZF_BLOCK_DTYPE, stop, consumed,
+    out_bytes)."""
+    L = load(lib_path)
+    b = _as_u8(gz)
+    blocks = np.zeros(max(int(max_blocks), 1), BGZF_BLOCK_DTYPE)
+    n, stop, consumed, out_bytes = C.c_uint32(), C.c_uint32(), C.c_uint64(), C.c_uint64()
+    rc = L.tgsf_text_bgzf_walk(b.ctypes.data, b.size, int(final), int(max_blocks), int(max_out_bytes), blocks.ctypes.data, C.byref(n), C.byref(stop),
+                               C.byref(consumed), C.byref(out_bytes))
+    if rc != 0:
+        raise TgsfError(rc, L.tgsf_text_last_error(None).decode())
+    return blocks[:n.value].copy(), stop.value, consumed.value, out_bytes.value
+
+
 class TextIndexer:
     """One tgsf_text object: device buffers for chunks of up to max_bytes bytes and max_records records, and a stream."""
 
     def __init__(self, device: int, max_bytes: int, max_records: int, lib_path: str | None = None):
-        self.lib = load(lib_path)
+        self.lib, self.lib_path = load(lib_path), lib_path
         self.max_bytes, self.max_records = int(max_bytes), int(max_records)
         h = C.c_void_p()
         rc = self.lib.tgsf_text_create(device, self.max_bytes, self.max_records, C.byref(h))
@@ -366,3 +425,80 @@ class TextIndexer:
         b = _as_u8(bam)
         return self._filter(lambda *a: self.lib.tgsf_text_bam_filter(self.h, ctx.h, b.ctypes.data, b.size, int(final), int(fastq_out), *a),
                             BamSummary(), out, out_capacity, frag_capacity, b.size // 50, want_results, True)
+
+    # ---- the BGZF input side: compressed members in ------------------------------------------------------------------------
+    def reserve_bgzf(self, max_gz_bytes, max_blocks):
+        """Once, before the first inflate: the device buffer for chunks of up to max_gz_bytes compressed bytes and the table
+        of up to max_blocks members."""
+        self._chk(self.lib.tgsf_text_bgzf_reserve(self.h, int(max_gz_bytes), int(max_blocks)))
+        self.max_gz_bytes, self.max_blocks = int(max_gz_bytes), int(max_blocks)
+
+    def inflate(self, gz, final=True, out_capacity=None, want_bytes=True):
+        """Inflate a chunk of BGZF members held in host memory into the object's text buffer: (the inflated bytes or None,
+        summary dict).  A bad member raises TgsfError(-6); its `summary` attribute holds bad_block."""
+        b = _as_u8(gz)
+        cap = self.max_bytes if out_capacity is None else int(out_capacity)
+        out = np.empty(max(cap, 1), np.uint8) if want_bytes else None
+        s = BgzfSummary()
+        self._chk(self.lib.tgsf_text_bgzf_inflate(self.h, b.ctypes.data, b.size, int(final), out.ctypes.data if want_bytes else None, cap, C.byref(s)), s)
+        return (out[:s.out_bytes].tobytes() if want_bytes else None), s.as_dict()
+
+    def inflate_device(self, n_bytes, blocks, walk_stop, d_out, out_capacity, d_gz=None, d_summary=None, stream=None):
+        """Enqueue the inflate of compressed bytes already in HBM (d_gz None: the object's buffer) into d_out without waiting;
+        blocks (BGZF_BLOCK_DTYPE) and walk_stop are bgzf_walk()'s."""
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        self._chk(self.lib.tgsf_text_bgzf_inflate_device(self.h, d_gz, int(n_bytes), blocks.ctypes.data if blocks.size else None, blocks.size, int(walk_stop),
+                                                         d_out, int(out_capacity), d_summary, stream))
+
+    def bam_walk_device(self, n_bytes, start=0, final=True, d_bam=None):
+        """The chain walk on BAM bytes in HBM (d_bam None: the object's BAM buffer) from byte `start` on: (rec_off of n + 1
+        entries, stop, consumed), offsets counted from d_bam, as bam_walk() gives them on the host."""
+        rec_off = np.zeros(self.max_records + 1, np.uint64)
+        n, stop, consumed = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        self._chk(self.lib.tgsf_text_bam_walk_device(self.h, d_bam, int(start), int(n_bytes), int(final), rec_off.ctypes.data, C.byref(n), C.byref(stop),
+                                                     C.byref(consumed)))
+        return rec_off[:n.value + 1].copy(), stop.value, consumed.value
+
+    # ---- compressed BAM in: chunks are (gz bytes that begin at a member, skip) ---------------------------------------------
+    def bgzf_bam_start(self, gz):
+        """Where the records of a .bam file begin, as a BGZF virtual offset (compressed offset of the member, skip): inflates
+        members from the front until the BAM header is complete."""
+        b = _as_u8(gz)
+        blocks, stop, consumed, out_bytes = bgzf_walk(b, self.max_blocks, self.max_bytes, False, self.lib_path)
+        ends = blocks["payload"] + blocks["clen"] + 8
+        k = 1
+        while True:
+            k = min(k, len(blocks))
+            data, _ = self.inflate(b[:int(ends[k - 1])] if k else b[:0], final=False)
+            try:
+                at = bam_header(data, self.lib_path)
+                break
+            except TgsfError:
+                if k >= len(blocks):
+                    raise
+                k *= 2
+        if at == len(data):
+            return (int(ends[k - 1]) if k else 0), 0
+        m = int(np.searchsorted(blocks["out"][:k], at, side="right")) - 1
+        return (int(ends[m - 1]) if m else 0), at - int(blocks["out"][m])
+
+    def bgzf_bam_decode(self, gz, skip=0, final=True, want_index=True):
+        """Decode a chunk of a .bam file as it is on disk, from a member's first byte on, the first `skip` inflated bytes left
+        out: (Index or None, summary dict with "gz", "bam", "next_gz", "next_skip")."""
+        b = _as_u8(gz)
+        arrs, ia = self._host_index() if want_index else (None, None)
+        s = BgzfBamSummary()
+        self._chk(self.lib.tgsf_text_bgzf_bam_decode(self.h, b.ctypes.data, b.size, int(skip), int(final), C.byref(ia) if want_index else None, C.byref(s)), s)
+        return (self._clip(arrs, s.n_records) if want_index else None), s.as_dict()
+
+    def bgzf_bam_submit(self, ctx, gz, skip=0, final=True, frag_capacity=None, want_index=True):
+        """Compressed BAM in, filter results out: as bam_submit()."""
+        b = _as_u8(gz)
+        return self._submit(lambda *a: self.lib.tgsf_text_bgzf_bam_submit(self.h, ctx.h, b.ctypes.data, b.size, int(skip), int(final), *a),
+                            BgzfBamSummary(), frag_capacity, b.size // 12, want_index, True)
+
+    def bgzf_bam_filter(self, ctx, gz, skip=0, final=True, fastq_out=True, out=None, out_capacity=None, frag_capacity=None, want_results=False):
+        """Compressed BAM in, clean text out: as bam_filter()."""
+        b = _as_u8(gz)
+        return self._filter(lambda *a: self.lib.tgsf_text_bgzf_bam_filter(self.h, ctx.h, b.ctypes.data, b.size, int(skip), int(final), int(fastq_out), *a),
+                            BgzfBamSummary(), out, out_capacity, frag_capacity, b.size // 12, want_results, True)
