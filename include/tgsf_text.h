@@ -482,6 +482,123 @@ int tgsf_text_bgzf_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, u
                               uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
                               tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out);
 
+/*
+ * ---- the BGZF output side: text in, compressed members out; and the CRC32 of inflated members --------------------------------
+ *
+ * THE RULE.  Truth is zlib.  The input in[0 .. n_bytes) is cut into members of TGSF_TEXT_BGZF_MEMBER input bytes, bgzip's size;
+ * the last member takes the rest; the cuts ignore record boundaries, as bgzip's do.  n_bytes == 0 has no member.  With eof the
+ * 28-byte EOF member of the BGZF specification ends the output.
+ *
+ *   - A member is 1f 8b 08 04 00 00 00 00 00 ff 06 00 'B' 'C' 02 00, BSIZE - 1 (u16), the payload, CRC32 (u32), ISIZE (u32):
+ *     26 bytes of framing.  A call is RIGHT iff, for every member, zlib's raw inflate of the payload ends a final block having
+ *     produced exactly the member's input bytes and consumed the payload to its last byte, and the trailer holds zlib.crc32 of
+ *     those bytes and their number.  gzip.decompress of the whole output then returns the input, and tgsf_text_bgzf_walk
+ *     (stricter than gzip) accepts every member.
+ *   - THE COMPRESSED BYTES THEMSELVES ARE NOT SPECIFIED.  They may change with the build and differ between the serial
+ *     emulation and the device.  The same input through the same build twice gives the same bytes.
+ *   - What this build writes: one block per member and no match search -- a dynamic block whose literal/length code is a
+ *     complete prefix code of at most 15 bits over the bytes that occur and symbol 256 (two codes of one bit when one byte
+ *     value occurs), whose distance code is two codes of one bit, and whose code-length code is constant; or one stored block
+ *     whenever the dynamic block would not be smaller.  So no payload exceeds its input by more than 5 bytes, and
+ *   - THE BOUND: tgsf_text_bgzf_bound(n_bytes, eof) = n_bytes + 31 * ceil(n_bytes / TGSF_TEXT_BGZF_MEMBER) + (eof ? 28 : 0)
+ *     is room enough for every input.
+ *   - Members begin at any byte address of the output.  No byte outside [out, out + summary.n_bytes) is written.  When
+ *     summary.n_bytes exceeds out_capacity NOTHING is written: stop is TGSF_TEXT_CAPACITY and n_bytes the size that is needed
+ *     (n_members and stored count what would have been written).
+ *   - member_end[i] is the byte behind member i, the EOF member included: n_members entries, ceil(n_bytes / MEMBER) + 1 at most.
+ *
+ * The CRC32 is computed on the device by the whole wave that has the member.  The same kernel checks input members:
+ * tgsf_text_bgzf_crc_device / tgsf_text_bgzf_verify close what THE RULE of the input side leaves open ("the CRC32 is not
+ * checked, as by the host") for a caller who asks; tgsf_text_bgzf_inflate and the composed calls stay as they are.
+ */
+#define TGSF_TEXT_BGZF_MEMBER 0xFF00u
+
+/* 40 bytes */
+typedef struct tgsf_text_gzout_summary {
+    uint64_t in_bytes;
+    uint64_t n_bytes;      /* compressed bytes; with TGSF_TEXT_CAPACITY the size that is needed                   */
+    uint32_t n_members;    /* members written, the EOF member included                                            */
+    uint32_t stored;       /* of them stored blocks                                                               */
+    uint32_t stop;         /* TGSF_TEXT_END, or TGSF_TEXT_CAPACITY: nothing was written                           */
+    float    device_ms;    /* the deflate kernels by HIP events, when tgsf_text_profile is on and the call synchronises; else 0 */
+    uint64_t reserved;
+} tgsf_text_gzout_summary;
+
+/* Host only.  UINT64_MAX when the sum does not fit 64 bits. */
+uint64_t tgsf_text_bgzf_bound(uint64_t n_bytes, int eof);
+
+/*
+ * Once, before the first deflate: a staging buffer for inputs of up to max_in_bytes (the host form's), the object's own
+ * compressed buffer of max_gz_bytes, per-member scratch (1 KiB a member).  No later call allocates.  A deflate before it is
+ * TGSF_E_INVALID, a second call is TGSF_E_INVALID, an input of n_bytes > max_in_bytes TGSF_E_CAPACITY before anything is
+ * copied or enqueued.
+ */
+int tgsf_text_bgzf_out_reserve(tgsf_text* tx, uint64_t max_in_bytes, uint64_t max_gz_bytes);
+
+/*
+ * Everything is in HBM; the work is enqueued on `hip_stream` (NULL: the object's own) and nothing is waited for.  d_in NULL:
+ * the object's own output buffer as the last format left it (after tgsf_text_out_reserve, else TGSF_E_INVALID); n_bytes is
+ * the caller's value, from tgsf_text_out_summary.  d_out NULL: the object's own compressed buffer, out_capacity capped by
+ * max_gz_bytes.  Both pointers must be 16-byte aligned; d_in is read up to n_bytes and not a byte further.  d_member_end
+ * (device, optional) and d_summary (device; NULL: the object's own) as THE RULE says.  The scratch is the object's: one call
+ * at a time, or all on one stream.
+ */
+int tgsf_text_bgzf_deflate_device(tgsf_text* tx, const uint8_t* d_in, uint64_t n_bytes, int eof, uint8_t* d_out, uint64_t out_capacity,
+                                  uint64_t* d_member_end, tgsf_text_gzout_summary* d_summary, void* hip_stream);
+
+/*
+ * The host form: the text goes up, the summary, summary.n_bytes bytes and member_end (optional) come down.  With
+ * TGSF_TEXT_CAPACITY only the summary comes down and the call returns TGSF_E_CAPACITY.
+ */
+int tgsf_text_bgzf_deflate(tgsf_text* tx, const uint8_t* in, uint64_t n_bytes, int eof, uint8_t* out, uint64_t out_capacity,
+                           uint64_t* member_end, tgsf_text_gzout_summary* out_summary);
+
+/*
+ * The opt-in CRC check of inflated members, after tgsf_text_bgzf_reserve.  blocks[0 .. n_blocks) is the HOST table of
+ * tgsf_text_bgzf_walk over the compressed bytes at d_gz (NULL: the object's buffer); d_inflated (NULL: the object's text
+ * buffer) holds what tgsf_text_bgzf_inflate_device made of them.  The table is checked as there (TGSF_E_INVALID, TGSF_E_CAPACITY
+ * above max_blocks) and goes up; a wave per member takes the CRC32 of its inflated bytes and compares it with the u32 in
+ * front of ISIZE.  *d_bad_crc (device) becomes the lowest mismatching member, UINT32_MAX: none.  Enqueued on `hip_stream`
+ * (NULL: the object's own); nothing is waited for.  The table on the device is the one the inflate uses: same stream.
+ * The first CRC check of an object brings the CRC32 tables up (4 KiB, one copy and one wait on the object's stream), unless
+ * tgsf_text_bgzf_out_reserve has; no later one allocates.
+ */
+int tgsf_text_bgzf_crc_device(tgsf_text* tx, const uint8_t* d_gz, const tgsf_text_bgzf_block* blocks, uint32_t n_blocks,
+                              const uint8_t* d_inflated, uint32_t* d_bad_crc, void* hip_stream);
+
+/*
+ * The host form of the check: tgsf_text_bgzf_inflate with out == NULL (the walk, the inflate into the text buffer, which it
+ * overwrites), then the CRC kernel.  *bad_block as there; *bad_crc the lowest member whose inflated bytes do not match its
+ * trailer, UINT32_MAX: none; it is meaningless at or behind a bad member.  TGSF_E_DATA naming the member when either is set.
+ * TGSF_OK SAYS THAT EVERY BYTE OF THE CHUNK WAS CHECKED, or, with final == 0, every byte in front of a last member that is
+ * cut short.  The call has no summary to say "so far", so whatever else the walk leaves over refuses it before anything is
+ * copied or enqueued (both words stay UINT32_MAX): a walk that stops as TGSF_TEXT_IRREGULAR -- bytes that are not a member
+ * (a damaged header, garbage behind the last member), or with final == 1 a member that is cut short -- is TGSF_E_DATA naming
+ * the member and the byte where it stopped; a walk that stops as TGSF_TEXT_CAPACITY (more members than max_blocks, or more
+ * inflated bytes than the text buffer) is TGSF_E_CAPACITY saying how many members fit and where the chunk goes on: a caller
+ * cuts there (tgsf_text_bgzf_walk) and checks piece by piece with final == 0.
+ */
+int tgsf_text_bgzf_verify(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint32_t* bad_block, uint32_t* bad_crc);
+
+/*
+ * COMPRESSED CLEAN TEXT OUT: tgsf_text_filter, tgsf_text_bam_filter and tgsf_text_bgzf_bam_filter with the deflate behind the
+ * format.  The arguments of their counterparts without rec_end (record ends mean nothing in compressed bytes), plus eof and
+ * gz_summary (may be NULL).  `out` receives the BGZF bytes, out_capacity counts them; out_summary still describes the text,
+ * which stays in the object's output buffer and is bounded by max_out_bytes alone.  After tgsf_text_out_reserve and
+ * tgsf_text_bgzf_out_reserve (max_in_bytes >= the text).  What the counterparts refuse is handed through unchanged.  No record:
+ * an empty output, or the EOF member alone.
+ */
+int tgsf_text_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
+                          uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary, tgsf_text_summary* in_summary,
+                          const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out, int eof, tgsf_text_gzout_summary* gz_summary);
+int tgsf_text_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
+                              uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary, tgsf_text_bam_summary* in_summary,
+                              const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out, int eof, tgsf_text_gzout_summary* gz_summary);
+int tgsf_text_bgzf_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final, int fastq_out,
+                                   uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary,
+                                   tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* batch_out,
+                                   int eof, tgsf_text_gzout_summary* gz_summary);
+
 #ifdef __cplusplus
 }
 #endif

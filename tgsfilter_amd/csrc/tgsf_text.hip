@@ -72,6 +72,21 @@ struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exa
     BgzfState* d_gstate = nullptr;
     tgsf_text_bgzf_summary* d_gsummary = nullptr;
     std::vector<tgsf_text_bgzf_block> h_gblocks;   // the walk of tgsf_text_bgzf_inflate
+    uint32_t* d_crc_tab = nullptr;      // the CRC32 tables of k_gz_count and k_bgzf_crc (either reserve brings them up)
+    // the BGZF output side (tgsf_text_bgzf_out_reserve): the host form's input, the compressed bytes, per-member scratch
+    bool zout_reserved = false;
+    uint64_t max_zin = 0, max_zout = 0;
+    uint32_t max_zmembers = 0;
+    uint8_t* d_zin = nullptr;           // max_zin rounded up to 16
+    uint8_t* d_zout = nullptr;          // max_zout rounded up to 16
+    GzMeta* d_zmeta = nullptr;          // codes, CRC32 and verdict of every member
+    uint64_t* d_zsize = nullptr;        // the members' sizes -> exclusive sums within blocks of kTextScanTile members
+    uint64_t* d_zsize_part = nullptr;   // ... and the blocks' offsets
+    uint64_t* d_zend = nullptr;         // the byte behind each member (the host form's member_end)
+    GzState* d_zstate = nullptr;
+    tgsf_text_gzout_summary* d_zsummary = nullptr;
+    rt_event zev[2] = {nullptr, nullptr};
+    bool zev_recorded = false;
     // around the last index, and around the stages of the last format (profile)
     rt_event ev[2] = {nullptr, nullptr};
     bool ev_recorded = false;
@@ -90,6 +105,7 @@ extern "C" void tgsf_text_destroy(tgsf_text* tx)
     if (tx->stream) { (void)rt_sync(tx->stream); rt_stream_destroy(tx->stream); }
     for (rt_event e : tx->ev) rt_event_destroy(e);
     for (rt_event e : tx->oev) rt_event_destroy(e);
+    for (rt_event e : tx->zev) rt_event_destroy(e);
     dev_free_all(tx);
     delete tx;
 }
@@ -464,12 +480,31 @@ extern "C" int tgsf_text_format_device(tgsf_text* tx, const uint8_t* d_text, con
                           out_capacity, d_rec_end, d_summary ? d_summary : tx->d_osummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
 }
 
-// format what is on the device into the object's output buffer, on its stream; summary, text and record ends come down
-static int format_down(tgsf_text* tx, const tgsf_read_result* d_reads, const tgsf_fragment* d_frags, uint32_t n_frags, int fastq_out,
-                       uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary)
+// where the format calls and the filter calls have the kept records formatted to; gz: as BGZF members (out and out_capacity are
+// theirs, the text stays in the object's output buffer; eof: the EOF member behind them; gz_summary may be NULL)
+struct FormatTo {
+    int fastq_out;
+    uint8_t* out;
+    uint64_t out_capacity;
+    uint64_t* rec_end;
+    tgsf_text_out_summary* out_summary;
+    int gz, eof;
+    tgsf_text_gzout_summary* gz_summary;
+};
+static int check_gzout(tgsf_text* tx, uint64_t n_bytes, int eof);
+static int gzout_down(tgsf_text* tx, const uint8_t* d_in, uint64_t n_bytes, int eof, uint8_t* out, uint64_t out_capacity, uint64_t* member_end,
+                      tgsf_text_gzout_summary* out_summary);
+
+// format what is on the device into the object's output buffer, on its stream; summary, text and record ends come down -- or,
+// with to.gz, the summary and the text's BGZF members
+static int format_down(tgsf_text* tx, const tgsf_read_result* d_reads, const tgsf_fragment* d_frags, uint32_t n_frags, const FormatTo& to)
 {
+    uint8_t* const out = to.out;
+    uint64_t* const rec_end = to.gz ? nullptr : to.rec_end;
+    tgsf_text_out_summary* const out_summary = to.out_summary;
+    const uint64_t out_capacity = to.gz ? tx->max_out : to.out_capacity;
     const uint64_t cap = std::min(out_capacity, tx->max_out);
-    int e = enqueue_format(tx, tx->d_text, tx->d_index, d_reads, d_frags, n_frags, fastq_out, tx->d_out, cap, rec_end ? tx->d_orec_end : nullptr,
+    int e = enqueue_format(tx, tx->d_text, tx->d_index, d_reads, d_frags, n_frags, to.fastq_out, tx->d_out, cap, rec_end ? tx->d_orec_end : nullptr,
                            tx->d_osummary, tx->stream);
     if (e) return e;
     tgsf_text_out_summary sum;
@@ -481,6 +516,10 @@ static int format_down(tgsf_text* tx, const tgsf_read_result* d_reads, const tgs
     if (sum.stop == TGSF_TEXT_CAPACITY)
         return fail(tx, TGSF_E_CAPACITY, "the formatted text has %llu bytes, there is room for %llu (out_capacity %llu, reserved %llu)",
                     (unsigned long long)sum.n_bytes, (unsigned long long)cap, (unsigned long long)out_capacity, (unsigned long long)tx->max_out);
+    if (to.gz) {
+        if ((e = check_gzout(tx, sum.n_bytes, to.eof))) return e;
+        return gzout_down(tx, tx->d_out, sum.n_bytes, to.eof, out, to.out_capacity, nullptr, to.gz_summary);
+    }
     if (sum.n_bytes) he |= rt_d2h(out, tx->d_out, (size_t)sum.n_bytes, tx->stream);
     if (rec_end && sum.n_records) he |= rt_d2h(rec_end, tx->d_orec_end, (size_t)sum.n_records * 8, tx->stream);
     if (!he) he = rt_sync(tx->stream);
@@ -504,7 +543,7 @@ extern "C" int tgsf_text_format(tgsf_text* tx, uint32_t n_records, int fasta, co
         he |= rt_h2d(tx->d_ofrags, frags, (size_t)n_frags * sizeof(tgsf_fragment), tx->stream);
     }
     if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
-    return format_down(tx, tx->d_reads, tx->d_ofrags, n_frags, fastq_out, out, out_capacity, rec_end, out_summary);
+    return format_down(tx, tx->d_reads, tx->d_ofrags, n_frags, {fastq_out, out, out_capacity, rec_end, out_summary});
 }
 
 // ---- the BAM input side --------------------------------------------------------------------------------------------------
@@ -730,14 +769,6 @@ struct Ingest {
     uint32_t skip;
 };
 static int bgzf_bam_decode_down(tgsf_text* tx, const Ingest& in, tgsf_text_bam_summary* bs);
-// where tgsf_text_filter and tgsf_text_bam_filter have the kept records formatted to
-struct FormatTo {
-    int fastq_out;
-    uint8_t* out;
-    uint64_t out_capacity;
-    uint64_t* rec_end;
-    tgsf_text_out_summary* out_summary;
-};
 
 // The chunk into the object, the one wait for the record count (libtgsf sizes its launches by n_reads on the host), the filter,
 // the index down last (the filter does not wait for it); with `to` the kept records as text.  The arguments have been checked.
@@ -751,6 +782,7 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
     tgsf_fragment* d_fr = down ? tx->d_frags : (to ? tx->d_ofrags : nullptr);
     const uint32_t fr_cap = down ? bo->frag_capacity : (to ? tx->max_frags : 0u);
     if (to) memset(to->out_summary, 0, sizeof *to->out_summary);
+    if (to && to->gz_summary) memset(to->gz_summary, 0, sizeof *to->gz_summary);
     tgsf_text_summary ts;
     tgsf_text_bam_summary bs;
     if (in.bam_summary) {
@@ -776,9 +808,11 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
     if ((e = run_filter(tx, ctx, n_records, in.bam_summary ? bs.text_bytes : in.n_bytes, bo, d_fr, fr_cap, &nf))) return e;
     if ((e = fetch_index(tx, out_index, n_records))) return e;
     if (in.text_summary) *in.text_summary = ts;
-    if (!to || !n_records) return TGSF_OK;                             // no record: nothing ran, an empty output, no error
+    if (!to) return TGSF_OK;
+    if (!n_records)                                                    // no record: nothing ran, an empty output (or the EOF member alone), no error
+        return to->gz ? gzout_down(tx, tx->d_out, 0, to->eof, to->out, to->out_capacity, nullptr, to->gz_summary) : TGSF_OK;
     if (nf > tx->max_frags) return fail(tx, TGSF_E_CAPACITY, "%u fragments, the output side was reserved for %u", nf, tx->max_frags);
-    return format_down(tx, tx->d_reads, d_fr, nf, to->fastq_out, to->out, to->out_capacity, to->rec_end, to->out_summary);
+    return format_down(tx, tx->d_reads, d_fr, nf, *to);
 }
 
 extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
@@ -892,6 +926,32 @@ extern "C" int tgsf_text_bgzf_reserve(tgsf_text* tx, uint64_t max_gz_bytes, uint
     return TGSF_OK;
 }
 
+// the CRC32 tables of the kernels (GzCrcTables: entry 256 * k + b is the register after byte b and k zero bytes), once per object:
+// tgsf_text_bgzf_out_reserve brings them up, or the first CRC check of an object that deflates nothing (4 KiB, one copy, one wait)
+struct CrcTables {
+    uint32_t t[1024];
+    CrcTables()
+    {
+        for (uint32_t i = 0; i < 1024u; i++) {
+            uint32_t c = i & 255u;
+            for (uint32_t k = 0; k < 8u * (1u + (i >> 8)); k++) c = (c >> 1) ^ (kCrcPoly & (0u - (c & 1u)));
+            t[i] = c;
+        }
+    }
+};
+static int crc_tables_up(tgsf_text* tx)
+{
+    static const CrcTables host;
+    if (tx->d_crc_tab) return 0;
+    uint32_t* d = nullptr;
+    if (dev_alloc(tx, &d, 1024)) return 1;
+    int he = rt_h2d(d, host.t, sizeof host.t, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return 1;
+    tx->d_crc_tab = d;
+    return 0;
+}
+
 // what every inflate is refused for before anything is copied or enqueued
 static int check_bgzf(tgsf_text* tx, uint64_t n_bytes)
 {
@@ -918,6 +978,23 @@ static int enqueue_bgzf(tgsf_text* tx, const uint8_t* d_gz, const tgsf_text_bgzf
     return TGSF_OK;
 }
 
+// a caller's table against the chunk's size and the rule's bounds: the kernels' bounds are these words.  *out: the inflated
+// bytes; *end: the byte behind the last payload.
+static int check_block_table(tgsf_text* tx, const tgsf_text_bgzf_block* blocks, uint32_t n_blocks, uint64_t n_bytes, uint64_t* out_bytes, uint64_t* last_end)
+{
+    uint64_t out = 0, end = 0;
+    for (uint32_t b = 0; b < n_blocks; b++) {
+        const tgsf_text_bgzf_block& k = blocks[b];
+        if (k.payload < end || k.payload > n_bytes || k.clen > n_bytes - k.payload || k.clen > TGSF_TEXT_BGZF_MAX_CLEN || k.usize > 65536u || k.out != out)
+            return fail(tx, TGSF_E_INVALID, "member %u of the block table is not what tgsf_text_bgzf_walk gives for a chunk of %llu bytes", b, (unsigned long long)n_bytes);
+        end = k.payload + k.clen;
+        out += k.usize;
+    }
+    *out_bytes = out;
+    *last_end = end;
+    return TGSF_OK;
+}
+
 extern "C" int tgsf_text_bgzf_inflate_device(tgsf_text* tx, const uint8_t* d_gz, uint64_t n_bytes, const tgsf_text_bgzf_block* blocks,
                                              uint32_t n_blocks, uint32_t walk_stop, uint8_t* d_out, uint64_t out_capacity,
                                              tgsf_text_bgzf_summary* d_summary, void* hip_stream)
@@ -931,17 +1008,38 @@ extern "C" int tgsf_text_bgzf_inflate_device(tgsf_text* tx, const uint8_t* d_gz,
     if (!d_gz) d_gz = tx->d_gz;
     if ((uintptr_t)d_gz & 15u) return fail(tx, TGSF_E_INVALID, "the compressed bytes on the device must be 16-byte aligned");
     uint64_t out = 0, end = 0;
-    for (uint32_t b = 0; b < n_blocks; b++) {                          // the kernel's bounds are these words
-        const tgsf_text_bgzf_block& k = blocks[b];
-        if (k.payload < end || k.payload > n_bytes || k.clen > n_bytes - k.payload || k.clen > TGSF_TEXT_BGZF_MAX_CLEN || k.usize > 65536u || k.out != out)
-            return fail(tx, TGSF_E_INVALID, "member %u of the block table is not what tgsf_text_bgzf_walk gives for a chunk of %llu bytes", b, (unsigned long long)n_bytes);
-        end = k.payload + k.clen;
-        out += k.usize;
-    }
+    if ((e = check_block_table(tx, blocks, n_blocks, n_bytes, &out, &end))) return e;
     if (out > out_capacity) return fail(tx, TGSF_E_CAPACITY, "the members inflate to %llu bytes, there is room for %llu", (unsigned long long)out, (unsigned long long)out_capacity);
     (void)rt_set_device(tx->device);
     return enqueue_bgzf(tx, d_gz, blocks, n_blocks, walk_stop, n_blocks ? end + 8 : 0, out, d_out, d_summary ? d_summary : tx->d_gsummary,
                         hip_stream ? (rt_stream)hip_stream : tx->stream);
+}
+
+// What tgsf_text_bgzf_inflate and tgsf_text_bgzf_verify share: the walk into h_gblocks (room: inflated bytes), the refusal of a
+// first member that does not fit, the bytes up, the inflate into the text buffer enqueued on the object's stream.
+struct GzWalk { uint32_t n, stop; uint64_t consumed, out_bytes; };
+static int walk_up_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint64_t room, GzWalk* w)
+{
+    if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
+    int e = check_bgzf(tx, n_bytes);
+    if (e) return e;
+    e = tgsf_text_bgzf_walk(gz, n_bytes, final, tx->max_gblocks, room, tx->h_gblocks.data(), &w->n, &w->stop, &w->consumed, &w->out_bytes);
+    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
+    if (!w->n && w->stop == TGSF_TEXT_CAPACITY)
+        return fail(tx, TGSF_E_CAPACITY, "the first member does not fit: room for %llu bytes (the text buffer %llu)", (unsigned long long)room, (unsigned long long)tx->max_bytes);
+    return TGSF_OK;
+}
+static int up_inflate(tgsf_text* tx, const uint8_t* gz, const GzWalk& w)
+{
+    (void)rt_set_device(tx->device);
+    const int he = w.consumed ? rt_h2d(tx->d_gz, gz, w.consumed, tx->stream) : 0;
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    return enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), w.n, w.stop, w.consumed, w.out_bytes, tx->d_text, tx->d_gsummary, tx->stream);
+}
+static int bad_member(tgsf_text* tx, uint32_t b)
+{
+    return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes", b,
+                (unsigned long long)tx->h_gblocks[b].payload, tx->h_gblocks[b].usize);
 }
 
 extern "C" int tgsf_text_bgzf_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint8_t* out, uint64_t out_capacity,
@@ -949,32 +1047,18 @@ extern "C" int tgsf_text_bgzf_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t
 {
     if (!tx) return TGSF_E_INVALID;
     if (!out_summary || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
-    int e = check_bgzf(tx, n_bytes);
+    GzWalk w;
+    int e = walk_up_inflate(tx, gz, n_bytes, final, out ? std::min(out_capacity, tx->max_bytes) : tx->max_bytes, &w);
+    if (!e) e = up_inflate(tx, gz, w);
     if (e) return e;
-    const uint64_t room = out ? std::min(out_capacity, tx->max_bytes) : tx->max_bytes;
-    uint32_t n = 0, walk_stop = 0;
-    uint64_t consumed = 0, out_bytes = 0;
-    e = tgsf_text_bgzf_walk(gz, n_bytes, final, tx->max_gblocks, room, tx->h_gblocks.data(), &n, &walk_stop, &consumed, &out_bytes);
-    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
-    if (!n && walk_stop == TGSF_TEXT_CAPACITY)
-        return fail(tx, TGSF_E_CAPACITY, "the first member does not fit: room for %llu bytes (out_capacity %llu, the text buffer %llu)",
-                    (unsigned long long)room, (unsigned long long)out_capacity, (unsigned long long)tx->max_bytes);
-    (void)rt_set_device(tx->device);
-    int he = consumed ? rt_h2d(tx->d_gz, gz, consumed, tx->stream) : 0;
-    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
-    if ((e = enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), n, walk_stop, consumed, out_bytes, tx->d_text, tx->d_gsummary, tx->stream))) return e;
     tgsf_text_bgzf_summary sum;
-    he = rt_d2h(&sum, tx->d_gsummary, sizeof sum, tx->stream);
-    if (!he && out && out_bytes) he = rt_d2h(out, tx->d_text, out_bytes, tx->stream);
+    int he = rt_d2h(&sum, tx->d_gsummary, sizeof sum, tx->stream);
+    if (!he && out && w.out_bytes) he = rt_d2h(out, tx->d_text, w.out_bytes, tx->stream);
     if (!he) he = rt_sync(tx->stream);
     if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
     sum.device_ms = index_ms(tx);
     *out_summary = sum;
-    if (sum.bad_block != 0xFFFFFFFFu)
-        return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes", sum.bad_block,
-                    (unsigned long long)tx->h_gblocks[sum.bad_block].payload, tx->h_gblocks[sum.bad_block].usize);
-    return TGSF_OK;
+    return sum.bad_block != 0xFFFFFFFFu ? bad_member(tx, sum.bad_block) : TGSF_OK;
 }
 
 // ---- compressed BAM in: the one-call forms, resumed by a BGZF virtual offset ---------------------------------------------------
@@ -1071,5 +1155,242 @@ extern "C" int tgsf_text_bgzf_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uin
     if (!e) e = check_bgzf_bam(tx, n_bytes, final);
     if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
+    return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &in_summary->bam, in_summary, skip}, out_index, bo, &to);
+}
+
+// ---- the BGZF output side: text in, compressed members out ------------------------------------------------------------------------
+extern "C" uint64_t tgsf_text_bgzf_bound(uint64_t n_bytes, int eof)
+{
+    const uint64_t members = n_bytes / kGzMember + (n_bytes % kGzMember ? 1u : 0u);
+    const uint64_t extra = (kGzFrame + 5u) * members + (eof ? kGzEofBytes : 0u);
+    return n_bytes > UINT64_MAX - extra ? UINT64_MAX : n_bytes + extra;
+}
+
+extern "C" int tgsf_text_bgzf_out_reserve(tgsf_text* tx, uint64_t max_in_bytes, uint64_t max_gz_bytes)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (tx->zout_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bgzf_out_reserve has been called already (%llu bytes in, %llu compressed)", (unsigned long long)tx->max_zin, (unsigned long long)tx->max_zout);
+    if (max_in_bytes == 0 || max_gz_bytes == 0) return fail(tx, TGSF_E_INVALID, "max_in_bytes and max_gz_bytes must be positive");
+    const uint64_t members = (max_in_bytes + kGzMember - 1) / kGzMember;
+    if (members >= 0xFFFFFFFFull) return fail(tx, TGSF_E_INVALID, "max_in_bytes of %llu: more members than 32 bits count", (unsigned long long)max_in_bytes);
+    (void)rt_set_device(tx->device);
+    for (rt_event& ev : tx->zev) if (!ev && rt_event_create(&ev)) return fail(tx, TGSF_E_HIP, "event creation failed");
+    int e = 0;
+    e |= dev_alloc(tx, &tx->d_zin, (max_in_bytes + 15u) & ~15ull);
+    if (!e) e |= dev_alloc(tx, &tx->d_zout, (max_gz_bytes + 15u) & ~15ull);
+    if (!e) e |= dev_alloc(tx, &tx->d_zmeta, (size_t)members);
+    if (!e) e |= dev_alloc(tx, &tx->d_zsize, (size_t)members + 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_zsize_part, (size_t)members / kTextScanTile + 2);
+    if (!e) e |= dev_alloc(tx, &tx->d_zend, (size_t)members + 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_zstate, 1);
+    if (!e) e |= dev_alloc(tx, &tx->d_zsummary, 1);
+    if (!e) e |= crc_tables_up(tx);
+    if (e) return fail(tx, TGSF_E_HIP, "device allocation failed (%llu bytes of text, %llu compressed)", (unsigned long long)max_in_bytes, (unsigned long long)max_gz_bytes);
+    tx->max_zin = max_in_bytes;
+    tx->max_zout = max_gz_bytes;
+    tx->max_zmembers = (uint32_t)members;
+    tx->zout_reserved = true;
+    return TGSF_OK;
+}
+
+// what every deflate is refused for before anything is copied or enqueued
+static int check_gzout(tgsf_text* tx, uint64_t n_bytes, int eof)
+{
+    if (!tx->zout_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bgzf_out_reserve has not been called on this object: no scratch to deflate with");
+    if (eof != 0 && eof != 1) return fail(tx, TGSF_E_INVALID, "eof is 0 or 1");
+    if (n_bytes > tx->max_zin)
+        return fail(tx, TGSF_E_CAPACITY, "text of %llu bytes to deflate, the object was reserved for %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_zin);
+    return TGSF_OK;
+}
+
+// the launches of one deflate, on st; nothing is waited for
+static int enqueue_gzout(tgsf_text* tx, const uint8_t* d_in, uint64_t n, int eof, uint8_t* d_out, uint64_t capacity, uint64_t* d_member_end,
+                         tgsf_text_gzout_summary* d_summary, rt_stream st)
+{
+    const uint32_t members = (uint32_t)((n + kGzMember - 1) / kGzMember);
+    const uint32_t nb = (members + kTextScanTile - 1) / kTextScanTile;
+    // a wave per member, at most a few per SIMD of the device: they stride
+    const unsigned g = grid_cap(std::min(std::max(blocks_for((uint64_t)members * kTextLanes, kTextThreads), 1u), 2048u));
+    GzState* S = tx->d_zstate;
+    const int he = rt_memset(S, 0, sizeof *S, st);
+    if (he) return fail(tx, TGSF_E_HIP, "device memset failed: %s", rt_errstr(he));
+    if (tx->profile) (void)rt_event_record(tx->zev[0], st);
+    if (members) {
+        TGSF_LAUNCH(k_gz_count, g, kTextThreads, st, d_in, n, members, (const uint32_t*)tx->d_crc_tab, tx->d_zmeta, tx->d_zsize, S);
+        TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_zsize, (uint64_t)members, tx->d_zsize_part);
+    }
+    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_zsize_part, nb, &S->total);
+    TGSF_LAUNCH(k_gz_emit, g, kTextThreads, st, d_in, n, members, eof, (const GzMeta*)tx->d_zmeta, (const uint64_t*)tx->d_zsize,
+                (const uint64_t*)tx->d_zsize_part, (const GzState*)S, capacity, d_out, d_member_end, d_summary);
+    if (tx->profile) { (void)rt_event_record(tx->zev[1], st); tx->zev_recorded = true; }
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bgzf_deflate_device(tgsf_text* tx, const uint8_t* d_in, uint64_t n_bytes, int eof, uint8_t* d_out, uint64_t out_capacity,
+                                             uint64_t* d_member_end, tgsf_text_gzout_summary* d_summary, void* hip_stream)
+{
+    if (!tx) return TGSF_E_INVALID;
+    const int e = check_gzout(tx, n_bytes, eof);
+    if (e) return e;
+    if (!d_in) {
+        if (!tx->out_reserved) return fail(tx, TGSF_E_INVALID, "no input: d_in is null and tgsf_text_out_reserve has not been called on this object");
+        if (n_bytes > tx->max_out) return fail(tx, TGSF_E_CAPACITY, "text of %llu bytes to deflate, the object's output buffer has %llu", (unsigned long long)n_bytes, (unsigned long long)tx->max_out);
+        d_in = tx->d_out;
+    }
+    if (((uintptr_t)d_in | (uintptr_t)d_out) & 15u) return fail(tx, TGSF_E_INVALID, "the device input and the device output buffer must be 16-byte aligned");
+    if (!d_out) { d_out = tx->d_zout; out_capacity = std::min(out_capacity, tx->max_zout); }
+    (void)rt_set_device(tx->device);
+    return enqueue_gzout(tx, d_in, n_bytes, eof, d_out, out_capacity, d_member_end, d_summary ? d_summary : tx->d_zsummary,
+                         hip_stream ? (rt_stream)hip_stream : tx->stream);
+}
+
+// deflate what is on the device into the object's compressed buffer, on its stream; summary, bytes and member ends come down
+static int gzout_down(tgsf_text* tx, const uint8_t* d_in, uint64_t n_bytes, int eof, uint8_t* out, uint64_t out_capacity, uint64_t* member_end,
+                      tgsf_text_gzout_summary* out_summary)
+{
+    const uint64_t cap = std::min(out_capacity, tx->max_zout);
+    const int e = enqueue_gzout(tx, d_in, n_bytes, eof, tx->d_zout, cap, member_end ? tx->d_zend : nullptr, tx->d_zsummary, tx->stream);
+    if (e) return e;
+    tgsf_text_gzout_summary sum;
+    int he = rt_d2h(&sum, tx->d_zsummary, sizeof sum, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    if (tx->profile && tx->zev_recorded) {
+        tx->zev_recorded = false;
+        if (rt_event_ms(&sum.device_ms, tx->zev[0], tx->zev[1])) { (void)rt_last_error(); sum.device_ms = 0.0f; }
+    }
+    if (out_summary) *out_summary = sum;
+    if (sum.stop == TGSF_TEXT_CAPACITY)
+        return fail(tx, TGSF_E_CAPACITY, "the compressed text has %llu bytes, there is room for %llu (out_capacity %llu, reserved %llu)",
+                    (unsigned long long)sum.n_bytes, (unsigned long long)cap, (unsigned long long)out_capacity, (unsigned long long)tx->max_zout);
+    if (sum.n_bytes) he |= rt_d2h(out, tx->d_zout, (size_t)sum.n_bytes, tx->stream);
+    if (member_end && sum.n_members) he |= rt_d2h(member_end, tx->d_zend, (size_t)sum.n_members * 8, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bgzf_deflate(tgsf_text* tx, const uint8_t* in, uint64_t n_bytes, int eof, uint8_t* out, uint64_t out_capacity,
+                                      uint64_t* member_end, tgsf_text_gzout_summary* out_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!out_summary || (!in && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument: summary, text or output buffer");
+    const int e = check_gzout(tx, n_bytes, eof);
+    if (e) return e;
+    (void)rt_set_device(tx->device);
+    const int he = n_bytes ? rt_h2d(tx->d_zin, in, n_bytes, tx->stream) : 0;
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    return gzout_down(tx, tx->d_zin, n_bytes, eof, out, out_capacity, member_end, out_summary);
+}
+
+// ---- the CRC32 of inflated members, for a caller who asks -------------------------------------------------------------------------
+// the check of the members in the object's table against their trailers, on st; *d_bad becomes the lowest that differs
+static int enqueue_crc(tgsf_text* tx, const uint8_t* d_gz, uint32_t n_blocks, const uint8_t* d_inflated, uint32_t* d_bad, rt_stream st)
+{
+    const int he = rt_memset(d_bad, 0xFF, 4, st);
+    if (he) return fail(tx, TGSF_E_HIP, "device memset failed: %s", rt_errstr(he));
+    const unsigned g = grid_cap(std::min(std::max(blocks_for((uint64_t)n_blocks * kTextLanes, kTextThreads), 1u), 2048u));
+    if (n_blocks)
+        TGSF_LAUNCH(k_bgzf_crc, g, kTextThreads, st, d_gz, (const tgsf_text_bgzf_block*)tx->d_gblocks, n_blocks, d_inflated, (const uint32_t*)tx->d_crc_tab, d_bad);
+    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bgzf_crc_device(tgsf_text* tx, const uint8_t* d_gz, const tgsf_text_bgzf_block* blocks, uint32_t n_blocks,
+                                         const uint8_t* d_inflated, uint32_t* d_bad_crc, void* hip_stream)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!tx->gz_reserved) return fail(tx, TGSF_E_INVALID, "tgsf_text_bgzf_reserve has not been called on this object: no table to check with");
+    if (!d_bad_crc || (!blocks && n_blocks)) return fail(tx, TGSF_E_INVALID, "null argument: the block table of tgsf_text_bgzf_walk, or the result's word");
+    if (n_blocks > tx->max_gblocks) return fail(tx, TGSF_E_CAPACITY, "%u members, the object was reserved for %u", n_blocks, tx->max_gblocks);
+    const uint64_t room = d_gz ? UINT64_MAX : tx->max_gz;             // (a caller's buffer: the table is the caller's word for its size)
+    uint64_t out = 0, end = 0;
+    int e = check_block_table(tx, blocks, n_blocks, room, &out, &end);
+    if (e) return e;
+    if (n_blocks && room - end < 8) return fail(tx, TGSF_E_INVALID, "the last member's trailer lies behind the %llu bytes of the object's buffer", (unsigned long long)room);
+    if (!d_inflated && out > tx->max_bytes) return fail(tx, TGSF_E_CAPACITY, "the members inflate to %llu bytes, the text buffer has %llu", (unsigned long long)out, (unsigned long long)tx->max_bytes);
+    (void)rt_set_device(tx->device);
+    if (crc_tables_up(tx)) return fail(tx, TGSF_E_HIP, "device allocation failed (the CRC32 tables)");
+    rt_stream st = hip_stream ? (rt_stream)hip_stream : tx->stream;
+    const int he = n_blocks ? rt_h2d(tx->d_gblocks, blocks, (size_t)n_blocks * sizeof *blocks, st) : 0;
+    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
+    return enqueue_crc(tx, d_gz ? d_gz : tx->d_gz, n_blocks, d_inflated ? d_inflated : tx->d_text, d_bad_crc, st);
+}
+
+extern "C" int tgsf_text_bgzf_verify(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint32_t* bad_block, uint32_t* bad_crc)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!bad_block || !bad_crc || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
+    *bad_block = *bad_crc = 0xFFFFFFFFu;
+    GzWalk w;
+    int e = walk_up_inflate(tx, gz, n_bytes, final, tx->max_bytes, &w);
+    if (e) return e;
+    // a check that covers a part of the bytes has no way to say so: whatever the walk leaves over refuses the call
+    if (w.stop == TGSF_TEXT_IRREGULAR)
+        return fail(tx, TGSF_E_DATA, "member %u of the chunk, at byte %llu of %llu, is not a BGZF member%s: nothing was checked", w.n, (unsigned long long)w.consumed,
+                    (unsigned long long)n_bytes, final ? ", or is cut short" : "");
+    if (w.stop == TGSF_TEXT_CAPACITY)
+        return fail(tx, TGSF_E_CAPACITY, "%u members (%llu inflated bytes) fit the object (max_blocks %u, the text buffer %llu) and the chunk goes on at byte %llu: nothing was checked",
+                    w.n, (unsigned long long)w.out_bytes, tx->max_gblocks, (unsigned long long)tx->max_bytes, (unsigned long long)w.consumed);
+    (void)rt_set_device(tx->device);
+    if (crc_tables_up(tx)) return fail(tx, TGSF_E_HIP, "device allocation failed (the CRC32 tables)");
+    if ((e = up_inflate(tx, gz, w))) return e;
+    if ((e = enqueue_crc(tx, tx->d_gz, w.n, tx->d_text, &tx->d_gstate->bad_crc, tx->stream))) return e;
+    BgzfState S;
+    int he = rt_d2h(&S, tx->d_gstate, sizeof S, tx->stream);
+    if (!he) he = rt_sync(tx->stream);
+    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    (void)index_ms(tx);
+    *bad_block = S.bad_block;
+    *bad_crc = S.bad_crc;
+    if (S.bad_block != 0xFFFFFFFFu) return bad_member(tx, S.bad_block);
+    if (S.bad_crc != 0xFFFFFFFFu)
+        return fail(tx, TGSF_E_DATA, "member %u of the chunk: the CRC32 of its %u inflated bytes is not the one in its trailer (byte %llu)", S.bad_crc,
+                    tx->h_gblocks[S.bad_crc].usize, (unsigned long long)(tx->h_gblocks[S.bad_crc].payload + tx->h_gblocks[S.bad_crc].clen));
+    return TGSF_OK;
+}
+
+// ---- compressed clean text out: the filter calls with the deflate behind the format ----------------------------------------------
+extern "C" int tgsf_text_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
+                                     uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary, tgsf_text_summary* in_summary,
+                                     const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo, int eof, tgsf_text_gzout_summary* gz_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!text && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, fasta, fastq_out);
+    if (!e) e = check_args(tx, n_bytes, fasta, final);
+    if (!e) e = check_gzout(tx, 0, eof);
+    if (e) return e;
+    const FormatTo to = {fastq_out, out, out_capacity, nullptr, out_summary, 1, eof, gz_summary};
+    return ingest_filter_format(tx, ctx, {text, n_bytes, fasta, final, in_summary, nullptr}, out_index, bo, &to);
+}
+
+extern "C" int tgsf_text_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
+                                         uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary, tgsf_text_bam_summary* in_summary,
+                                         const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo, int eof, tgsf_text_gzout_summary* gz_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!bam && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, 0, fastq_out);
+    if (!e) e = check_bam(tx, n_bytes, final);
+    if (!e) e = check_gzout(tx, 0, eof);
+    if (e) return e;
+    const FormatTo to = {fastq_out, out, out_capacity, nullptr, out_summary, 1, eof, gz_summary};
+    return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
+}
+
+extern "C" int tgsf_text_bgzf_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final, int fastq_out,
+                                              uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary,
+                                              tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo,
+                                              int eof, tgsf_text_gzout_summary* gz_summary)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!gz && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = check_format(tx, 0, 0, fastq_out);
+    if (!e) e = check_bgzf_bam(tx, n_bytes, final);
+    if (!e) e = check_gzout(tx, 0, eof);
+    if (e) return e;
+    const FormatTo to = {fastq_out, out, out_capacity, nullptr, out_summary, 1, eof, gz_summary};
     return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &in_summary->bam, in_summary, skip}, out_index, bo, &to);
 }

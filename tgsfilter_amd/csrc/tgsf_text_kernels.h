@@ -821,7 +821,7 @@ TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bam_unpack(const uint8_t* __restrict_
 //
 // EVERY LOOP IS BOUNDED BY clen AND usize: an iteration of the symbol loop consumes at least one bit or ends the member, a
 // block at least three, and a member ends as BAD as soon as a consumed bit lies behind 8 * clen or a byte behind usize.
-struct BgzfState { uint32_t bad_block, reserved; };     // the lowest bad member (0xFFFFFFFF: none)
+struct BgzfState { uint32_t bad_block, bad_crc; };      // the lowest bad member; the lowest whose CRC32 differs, when asked (0xFFFFFFFF: none)
 
 constexpr uint32_t kInfWaves = kTextThreads / 64;         // table sets of a workgroup: its waves (the emulation's lanes, waves of one
                                                           // that run one after the other, take turns on them)
@@ -1066,6 +1066,385 @@ TGSF_KERNEL k_bgzf_finish(uint32_t n_blocks, uint32_t walk_stop, uint64_t consum
     out->bad_block = S->bad_block;
     out->device_ms = 0.0f;
     out->reserved = 0;
+}
+
+// ---- the BGZF output side: text -> compressed members, and the CRC32 both ends need (tgsf_text_bgzf_deflate*, _crc_device) ------
+//
+//   k_gz_count         a wave per member of TGSF_TEXT_BGZF_MEMBER input bytes, the waves striding over the members.  One read of
+//                      the member, a contiguous slice per lane: the histogram (LDS, a set per wave) and the slice's CRC32, the
+//                      slices' CRCs combined by multiplication by x^(8 * bytes behind the slice) mod P.  Then the prefix code:
+//                      the symbols ranked by frequency (a symbol per lane), the Huffman depths by the in-place method of Moffat
+//                      and Katajainen (one lane: 3 passes over at most 257 words), depths over 15 clamped and the Kraft sum
+//                      repaired as zlib's gen_bitlen does (a leaf one level down, a 15-bit leaf beside it, until the code is
+//                      complete), canonical codes (a symbol per lane).  Per member to scratch: code | length << 16 of every
+//                      symbol, the CRC, stored or not; its size in bytes, framing included, to the table that is scanned.
+//   (k_text_scan_tiles<uint64_t> / k_textout_scan_top: exclusive prefix sums of the sizes -- a member's place in the output)
+//   k_gz_emit          a wave per member, straight to its final place: the 18 bytes of header, the block, CRC32 and ISIZE.  A
+//                      dynamic block goes through a staging area in LDS, 16 input bytes a lane and round (one aligned load, the
+//                      loads of a wave side by side): a lane's codes are put together in registers, its bit offset is the wave's
+//                      prefix sum of code lengths, the words it shares with its neighbours are or-ed in LDS; whole dwords then
+//                      leave for the output, the bits left over open the next round.  Decides CAPACITY (nothing is written),
+//                      writes the EOF member, the summary and member_end.
+//   k_bgzf_crc         a wave per member of a block table: CRC32 of its inflated bytes against its trailer
+//
+// EVERY LOOP IS BOUNDED BY THE MEMBER'S SIZE OR BY THE ALPHABET'S: no input byte steers a loop count.
+constexpr uint32_t kGzMember = TGSF_TEXT_BGZF_MEMBER;
+constexpr uint32_t kGzSyms = 257;                          // the literals and the end of the block: no length symbol occurs
+constexpr uint32_t kGzSymRoom = 260;
+constexpr uint32_t kGzFrame = 26;                          // header 18, CRC32, ISIZE
+constexpr uint32_t kGzEofBytes = 28;
+// a dynamic block's header: BFINAL, BTYPE, HLIT = 257, HDIST = 2, HCLEN = 19; the code-length code (three bits each: four-bit
+// codes for 0..15, none for 16, 17, 18: constant and complete); 257 + 2 code lengths of four bits
+constexpr uint32_t kGzFixedHeadBits = 17 + 19 * 3;
+constexpr uint32_t kGzHeadBits = kGzFixedHeadBits + 4 * (kGzSyms + 2);
+constexpr uint32_t kGzRound = 16 * kTextLanes;             // input bytes of a round of k_gz_emit
+// the staging area: the bits left over (31 at most), a round's (15 a byte at most), and the word a put may reach into
+constexpr uint32_t kGzStageWords = (31 + 15 * kGzRound + 31) / 32 + 2 > 40 ? (31 + 15 * kGzRound + 31) / 32 + 2 : 40;
+static_assert(kGzStageWords * 32 >= kGzHeadBits + 64, "the staging area holds the block's header");
+static_assert(kGzMember % 16 == 0 && kGzMember + 5 + kGzFrame <= 65536, "members begin on 16 bytes of the input; BSIZE - 1 is 16 bits");
+
+struct GzState { uint64_t total; uint32_t stored, reserved; };        // bytes of all members but the EOF member; stored members
+struct GzMeta { uint32_t crc, stored; uint32_t lut[kGzSyms]; uint32_t reserved; };   // lut[s]: the code, its first bit lowest | length << 16
+struct GzCrcTables { uint32_t t[4][256]; };                // t[k][b]: the register after byte b and k zero bytes (slicing by 4)
+struct GzCountWave { uint32_t hist[kGzSymRoom], freq[kGzSymRoom]; uint16_t order[kGzSymRoom]; uint8_t lens[kGzSymRoom]; uint32_t cnt[16]; };
+struct GzEmitWave { uint32_t lut[kGzSymRoom]; uint32_t stage[kGzStageWords]; };
+
+#if !defined(TGSF_EMUL)
+TGSF_D uint32_t wave_xor(uint32_t v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v ^= (uint32_t)__shfl_xor((int)v, o, 64);
+    return v;
+}
+#else
+TGSF_HD uint32_t wave_xor(uint32_t v) { return v; }
+#endif
+
+constexpr uint32_t kCrcPoly = 0xEDB88320u;                 // IEEE, reflected: bit 31 is x^0
+// crc_tab[256 * k + b] -> LDS, by the workgroup (the host computed it: tgsf_text.hip)
+TGSF_D void gz_crc_tables(GzCrcTables& T, const uint32_t* __restrict__ crc_tab)
+{
+    for (uint32_t i = TGSF_COOP_BEGIN; i < 1024u; i += TGSF_COOP_STRIDE) T.t[i >> 8][i & 255u] = crc_tab[i];
+    TGSF_BLOCK_SYNC();
+}
+TGSF_D uint32_t gz_crc_byte(const GzCrcTables& T, uint32_t c, uint32_t b) { return (c >> 8) ^ T.t[0][(c ^ b) & 255u]; }
+TGSF_D uint32_t gz_crc_word(const GzCrcTables& T, uint32_t c, uint32_t w)      // four bytes, the first lowest
+{
+    c ^= w;
+    return T.t[3][c & 255u] ^ T.t[2][(c >> 8) & 255u] ^ T.t[1][(c >> 16) & 255u] ^ T.t[0][c >> 24];
+}
+// a * b mod P
+TGSF_HD uint32_t gz_mulmod(uint32_t a, uint32_t b)
+{
+    uint32_t p = 0;
+    for (uint32_t i = 0; i < 32u; i++) {
+        p ^= b & (0u - ((a >> (31u - i)) & 1u));
+        b = (b >> 1) ^ (kCrcPoly & (0u - (b & 1u)));
+    }
+    return p;
+}
+// x^(8 n) mod P, n < 2^17
+TGSF_HD uint32_t gz_xpow8(uint32_t n)
+{
+    uint32_t p = 0x80000000u, sq = 0x00800000u;            // 1; x^8
+    for (uint32_t i = 0; i < 17u; i++, n >>= 1) {
+        if (n & 1u) p = gz_mulmod(sq, p);
+        sq = gz_mulmod(sq, sq);
+    }
+    return p;
+}
+// zlib.crc32 of p[0 .. len) by one lane, at any alignment: bytes up to the first 16-byte boundary, aligned chunks, bytes; with
+// Hist every byte is counted in hist[] (LDS)
+template <bool Hist>
+TGSF_D uint32_t gz_crc_slice(const GzCrcTables& T, const uint8_t* __restrict__ p, uint32_t len, uint32_t* hist)
+{
+    uint32_t c = 0xFFFFFFFFu, i = 0;
+    uint32_t head = (16u - (uint32_t)((uintptr_t)p & 15u)) & 15u;
+    if (head > len) head = len;
+    for (; i < head; i++) { const uint32_t b = p[i]; c = gz_crc_byte(T, c, b); if (Hist) atomicAdd(&hist[b], 1u); }
+    for (; i + 16u <= len; i += 16u) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p + i);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; k++) {
+            c = gz_crc_word(T, c, w[k]);
+            if (Hist) { atomicAdd(&hist[w[k] & 255u], 1u); atomicAdd(&hist[(w[k] >> 8) & 255u], 1u); atomicAdd(&hist[(w[k] >> 16) & 255u], 1u); atomicAdd(&hist[w[k] >> 24], 1u); }
+        }
+    }
+    for (; i < len; i++) { const uint32_t b = p[i]; c = gz_crc_byte(T, c, b); if (Hist) atomicAdd(&hist[b], 1u); }
+    return ~c;
+}
+// ... of p[0 .. n) by the wave, n <= 65536: a slice of whole 16-byte chunks per lane; crc(A B) = crc(A) x^(8 |B|) + crc(B)
+template <bool Hist>
+TGSF_D uint32_t gz_crc_wave(const GzCrcTables& T, const uint8_t* __restrict__ p, uint32_t n, uint32_t* hist)
+{
+    const uint32_t per = ((n + kTextLanes - 1u) / kTextLanes + 15u) & ~15u;
+    uint32_t lo = text_lane() * per, hi = lo + per;
+    if (lo > n) lo = n;
+    if (hi > n) hi = n;
+    const uint32_t c = gz_crc_slice<Hist>(T, p + lo, hi - lo, hist);
+    return wave_xor(hi > lo ? gz_mulmod(c, gz_xpow8(n - hi)) : 0u);
+}
+
+// freq[0 .. n), ascending, n >= 2 -> the depth of each in a Huffman tree, in place (Moffat and Katajainen 1995); one lane
+TGSF_D void gz_depths(uint32_t* A, uint32_t n)
+{
+    A[0] += A[1];
+    uint32_t root = 0, leaf = 2;
+    for (uint32_t next = 1; next + 1 < n; next++) {                    // parents: A[k] of an internal node is its parent's index
+        if (leaf >= n || A[root] < A[leaf]) { A[next] = A[root]; A[root++] = next; } else A[next] = A[leaf++];
+        if (leaf >= n || (root < next && A[root] < A[leaf])) { A[next] += A[root]; A[root++] = next; } else A[next] += A[leaf++];
+    }
+    A[n - 2] = 0;
+    for (uint32_t next = n - 2; next-- > 0;) A[next] = A[A[next]] + 1u;  // depths of the internal nodes
+    uint32_t avbl = 1, used = 0, dpth = 0;
+    int32_t r = (int32_t)n - 2, nx = (int32_t)n - 1;
+    while (avbl > 0 && nx >= 0) {                                      // depths of the leaves, a level a turn: at most n turns
+        while (r >= 0 && A[r] == dpth) { used++; r--; }
+        while (avbl > used && nx >= 0) { A[nx--] = dpth; avbl--; }
+        avbl = 2u * used; dpth++; used = 0;
+    }
+}
+
+// one member: in[0 .. usize), 1 <= usize <= kGzMember, 16-byte aligned.  Returns its payload's bytes (wave-uniform).
+TGSF_D uint32_t gz_count_member(const GzCrcTables& T, const uint8_t* __restrict__ in, uint32_t usize, GzCountWave& W, GzMeta* M)
+{
+    [[maybe_unused]] const uint32_t lane = text_lane();               // (the emulation's loops take every turn themselves)
+    TGSF_WAVE_SYNC();                                                  // the last member's reads of W are over
+    for (uint32_t s = TGSF_WCOOP_BEGIN(lane); s < kGzSymRoom; s += TGSF_WCOOP_STRIDE) { W.hist[s] = s == 256u ? 1u : 0u; W.lens[s] = 0; }
+    TGSF_WAVE_SYNC();
+    const uint32_t crc = gz_crc_wave<true>(T, in, usize, W.hist);
+    TGSF_WAVE_SYNC();
+    // the symbols that occur, by frequency (then by value): each finds its own rank
+    uint32_t mine = 0;
+    for (uint32_t s = TGSF_WCOOP_BEGIN(lane); s < kGzSyms; s += TGSF_WCOOP_STRIDE) {
+        const uint32_t f = W.hist[s];
+        if (!f) continue;
+        const uint32_t key = f << 9 | s;                               // (f <= kGzMember < 2^16)
+        uint32_t rank = 0;
+        for (uint32_t t = 0; t < kGzSyms; t++) { const uint32_t ft = W.hist[t]; rank += ft && (ft << 9 | t) < key ? 1u : 0u; }
+        W.freq[rank] = f;
+        W.order[rank] = (uint16_t)s;
+        mine++;
+    }
+    const uint32_t n_used = (uint32_t)wave_sum_i32((int32_t)mine);     // two at least: a byte and the end of the block
+    TGSF_WAVE_SYNC();
+    if (wave_leader()) gz_depths(W.freq, n_used);
+    TGSF_WAVE_SYNC();
+    for (uint32_t l = TGSF_WCOOP_BEGIN(lane); l < 16u; l += TGSF_WCOOP_STRIDE) {    // codes per length, depths over 15 clamped
+        uint32_t c = 0;
+        for (uint32_t i = 0; i < n_used; i++) { const uint32_t d = W.freq[i]; c += (d < 15u ? d : 15u) == l ? 1u : 0u; }
+        W.cnt[l] = c;
+    }
+    TGSF_WAVE_SYNC();
+    if (wave_leader()) {
+        // The clamped set is over-subscribed by a whole number of 2^-15: every step takes one away.  There is a leaf above level
+        // 15 as long as the sum exceeds 1 (n_used leaves of 15 bits sum to less), and a 15-bit leaf (the clamped ones: more of
+        // them than steps).
+        uint32_t kraft = 0;
+        for (uint32_t l = 1; l < 16u; l++) kraft += W.cnt[l] << (15u - l);
+        for (; kraft > 32768u; kraft--) {
+            uint32_t b = 14;
+            while (b > 1u && !W.cnt[b]) b--;
+            W.cnt[b]--; W.cnt[b + 1u] += 2u; W.cnt[15]--;
+        }
+    }
+    TGSF_WAVE_SYNC();
+    for (uint32_t i = TGSF_WCOOP_BEGIN(lane); i < n_used; i += TGSF_WCOOP_STRIDE) {  // the rarest symbols get the longest codes
+        uint32_t acc = 0, bits = 1;
+        for (uint32_t l = 15; l >= 1u; l--) { acc += W.cnt[l]; if (i < acc) { bits = l; break; } }
+        W.lens[W.order[i]] = (uint8_t)bits;
+    }
+    TGSF_WAVE_SYNC();
+    uint64_t bits = 0;
+    for (uint32_t s = TGSF_WCOOP_BEGIN(lane); s < kGzSyms; s += TGSF_WCOOP_STRIDE) {  // canonical codes
+        const uint32_t l = W.lens[s];
+        uint32_t e = 0;
+        if (l) {
+            uint32_t code = 0, rev = 0;
+            for (uint32_t k = 1; k < l; k++) code = (code + W.cnt[k]) << 1;
+            for (uint32_t t = 0; t < s; t++) code += W.lens[t] == l ? 1u : 0u;
+            for (uint32_t k = 0; k < l; k++) rev = rev << 1 | ((code >> k) & 1u);
+            e = rev | l << 16;
+        }
+        M->lut[s] = e;
+        bits += (uint64_t)W.hist[s] * l;
+    }
+    const uint32_t dyn = (uint32_t)((wave_sum(bits) + kGzHeadBits + 7u) / 8u);
+    const bool stored = dyn >= usize + 5u;                             // one stored block whenever the dynamic one is not smaller
+    if (wave_leader()) { M->crc = crc; M->stored = stored ? 1u : 0u; M->reserved = 0; }
+    return stored ? usize + 5u : dyn;
+}
+
+TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_gz_count(const uint8_t* __restrict__ in, uint64_t n, uint32_t n_members,
+                                                    const uint32_t* __restrict__ crc_tab, GzMeta* __restrict__ meta,
+                                                    uint64_t* __restrict__ size, GzState* S)
+{
+    TGSF_SHARED GzCrcTables T;
+    TGSF_SHARED GzCountWave sets[kInfWaves];
+    gz_crc_tables(T, crc_tab);
+    GzCountWave& W = sets[(threadIdx.x / kTextLanes) % kInfWaves];
+    const uint64_t n_waves = gridDim.x * (uint64_t)blockDim.x / kTextLanes;
+    uint32_t stored = 0;
+    for (uint64_t m = wave_uniform64(text_wave()); m < n_members; m += n_waves) {
+        const uint64_t at = m * kGzMember;
+        const uint32_t usize = n - at < kGzMember ? (uint32_t)(n - at) : kGzMember;
+        const uint32_t payload = wave_first(gz_count_member(T, in + at, usize, W, meta + m));
+        if (wave_leader()) size[m] = (uint64_t)payload + kGzFrame;
+        stored += payload == usize + 5u ? 1u : 0u;
+    }
+    if (wave_leader() && stored) atomicAdd(&S->stored, stored);
+}
+
+// 1f 8b 08 04 00 00 00 00 00 ff 06 00 'B' 'C' 02 00: a member's first 16 bytes; the EOF member goes on 1b 00 03 00 and 8 zeros
+constexpr uint64_t kGzHeadLo = 0x0000000004088B1Full, kGzHeadHi = 0x000243420006FF00ull, kGzEofTail = 0x000000000003001Bull;
+TGSF_HD uint8_t gz_head_byte(uint32_t i) { return (uint8_t)((i < 8u ? kGzHeadLo >> (8u * i) : kGzHeadHi >> (8u * (i - 8u))) & 0xFFu); }
+TGSF_HD uint8_t gz_eof_byte(uint32_t i) { return i < 16u ? gz_head_byte(i) : (uint8_t)(i < 24u ? (kGzEofTail >> (8u * (i - 16u))) & 0xFFu : 0u); }
+
+// the low nbits <= 32 bits of v (nothing above them) into the staging area at bit `pos`
+TGSF_D void gz_put(uint32_t* stage, uint32_t pos, uint32_t v, uint32_t nbits)
+{
+    const uint32_t w = pos >> 5, sh = pos & 31u;
+    atomicOr(&stage[w], v << sh);
+    if (sh + nbits > 32u) atomicOr(&stage[w + 1u], v >> (32u - sh));
+}
+// The staging area's bits [0, pos) leave for dst: its whole dwords, the bits left over move to the front (last: every byte
+// that holds a bit).  Wave-uniform but for the copy.
+TGSF_D void gz_flush(uint32_t* stage, uint32_t& pos, uint8_t*& dst, bool last)
+{
+    TGSF_WAVE_SYNC();
+    const uint32_t nw = pos >> 5, nbytes = last ? (pos + 7u) / 8u : 4u * nw;
+    for (uint32_t i = text_lane(); i < nbytes; i += kTextLanes) dst[i] = (uint8_t)(stage[i >> 2] >> (8u * (i & 3u)));
+    if (last) return;
+    const uint32_t carry = wave_first(stage[nw]);
+    TGSF_WAVE_SYNC();
+    for (uint32_t w = TGSF_WCOOP_BEGIN(text_lane()); w <= nw; w += TGSF_WCOOP_STRIDE) stage[w] = w == 0 ? carry : 0u;
+    TGSF_WAVE_SYNC();
+    dst += 4u * nw;
+    pos &= 31u;
+}
+
+// one member to out[0 .. bsize): the frame, then one stored or one dynamic block of in[0 .. usize)
+TGSF_D void gz_emit_member(const uint8_t* __restrict__ in, uint32_t usize, const GzMeta* __restrict__ M, uint8_t* out, uint32_t bsize, GzEmitWave& E)
+{
+    const uint32_t lane = text_lane();
+    const uint32_t crc = wave_first(M->crc);
+    const bool stored = wave_first(M->stored) != 0;
+    for (uint32_t i = TGSF_WCOOP_BEGIN(lane); i < kGzFrame; i += TGSF_WCOOP_STRIDE) {
+        if (i < 16u) out[i] = gz_head_byte(i);
+        else if (i < 18u) out[i] = (uint8_t)((bsize - 1u) >> (8u * (i - 16u)));
+        else if (i < 22u) out[bsize - 26u + i] = (uint8_t)(crc >> (8u * (i - 18u)));
+        else out[bsize - 26u + i] = (uint8_t)(usize >> (8u * (i - 22u)));
+    }
+    uint8_t* dst = out + 18;
+    if (stored) {                                                      // BFINAL, BTYPE 0, to the byte boundary; LEN, NLEN; the bytes
+        for (uint32_t i = TGSF_WCOOP_BEGIN(lane); i < 5u; i += TGSF_WCOOP_STRIDE)
+            dst[i] = (uint8_t)(i == 0 ? 1u : ((i < 3u ? usize : ~usize) >> (8u * ((i - 1u) & 1u))));
+        for (uint32_t i = lane; i < usize; i += kTextLanes) dst[5u + i] = in[i];
+        return;
+    }
+    TGSF_WAVE_SYNC();                                                  // the last member's reads of E are over
+    for (uint32_t s = TGSF_WCOOP_BEGIN(lane); s < kGzSyms; s += TGSF_WCOOP_STRIDE) E.lut[s] = M->lut[s];
+    for (uint32_t w = TGSF_WCOOP_BEGIN(lane); w < kGzStageWords; w += TGSF_WCOOP_STRIDE) E.stage[w] = 0;
+    TGSF_WAVE_SYNC();
+    // the block's header: entry 0 is its constant front, entry 1 + s the length of symbol s, the last two the distance code
+    // (two codes of one bit, as zlib writes when no distance occurs)
+    for (uint32_t j = TGSF_WCOOP_BEGIN(lane); j < kGzSyms + 3u; j += TGSF_WCOOP_STRIDE) {
+        if (j == 0) {
+            gz_put(E.stage, 0, 1u | 2u << 1 | 0u << 3 | 1u << 8 | 15u << 13, 17);
+            for (uint32_t k = 3; k < 19u; k++) gz_put(E.stage, 17u + 3u * k, 4u, 3);      // (inf_order: 16, 17, 18 come first)
+        } else {
+            const uint32_t l = j - 1u < kGzSyms ? E.lut[j - 1u] >> 16 : 1u;
+            gz_put(E.stage, kGzFixedHeadBits + 4u * (j - 1u), (l & 1u) << 3 | (l & 2u) << 1 | (l & 4u) >> 1 | (l & 8u) >> 3, 4);
+        }
+    }
+    uint32_t pos = kGzHeadBits;
+    gz_flush(E.stage, pos, dst, false);
+    for (uint32_t r0 = 0; r0 < usize; r0 += kGzRound) {
+        const uint32_t off = r0 + lane * 16u;
+        const uint32_t nb = off < usize ? (usize - off < 16u ? usize - off : 16u) : 0u;
+        uint64_t lo = 0, hi = 0;
+        if (nb == 16u) {
+            const uint4 v = *reinterpret_cast<const uint4*>(in + off);
+            lo = (uint64_t)v.y << 32 | v.x; hi = (uint64_t)v.w << 32 | v.z;
+        } else
+            for (uint32_t i = 0; i < nb; i++) { const uint64_t b = in[off + i]; if (i < 8) lo |= b << (8u * i); else hi |= b << (8u * (i - 8u)); }
+        uint32_t e[16], bits = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 16u; i++) {
+            const uint32_t b = (uint32_t)((i < 8 ? lo >> (8u * i) : hi >> (8u * (i - 8u))) & 0xFFu);
+            e[i] = i < nb ? E.lut[b] : 0u;
+            bits += e[i] >> 16;
+        }
+        uint32_t p = pos + wave_excl_scan(bits);
+        pos += (uint32_t)wave_sum_i32((int32_t)bits);
+        uint64_t acc = 0;
+        uint32_t na = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < 16u; i++) {
+            acc |= (uint64_t)(e[i] & 0xFFFFu) << na;
+            na += e[i] >> 16;
+            if (na >= 32u) { gz_put(E.stage, p, (uint32_t)acc, 32); acc >>= 32; na -= 32u; p += 32u; }
+        }
+        if (na) gz_put(E.stage, p, (uint32_t)acc, na);
+        gz_flush(E.stage, pos, dst, false);
+    }
+    const uint32_t eob = wave_first(E.lut[256]);
+    if (wave_leader()) gz_put(E.stage, pos, eob & 0xFFFFu, eob >> 16);
+    pos += eob >> 16;
+    gz_flush(E.stage, pos, dst, true);
+}
+
+TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_gz_emit(const uint8_t* __restrict__ in, uint64_t n, uint32_t n_members, int eof,
+                                                   const GzMeta* __restrict__ meta, const uint64_t* __restrict__ size_excl,
+                                                   const uint64_t* __restrict__ size_part, const GzState* S, uint64_t capacity,
+                                                   uint8_t* out, uint64_t* __restrict__ member_end, tgsf_text_gzout_summary* sum)
+{
+    TGSF_SHARED GzEmitWave sets[kInfWaves];
+    GzEmitWave& E = sets[(threadIdx.x / kTextLanes) % kInfWaves];
+    const uint64_t body = S->total, total = body + (eof ? kGzEofBytes : 0u);
+    const bool fits = total <= capacity;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sum->in_bytes = n;
+        sum->n_bytes = total;
+        sum->n_members = n_members + (eof ? 1u : 0u);
+        sum->stored = S->stored;
+        sum->stop = fits ? TGSF_TEXT_END : TGSF_TEXT_CAPACITY;
+        sum->device_ms = 0.0f;
+        sum->reserved = 0;
+    }
+    if (!fits) return;                                                 // TGSF_TEXT_CAPACITY: nothing is written
+    const uint64_t n_waves = gridDim.x * (uint64_t)blockDim.x / kTextLanes;
+    for (uint64_t m = wave_uniform64(text_wave()); m < n_members; m += n_waves) {
+        const uint64_t at = m * kGzMember;
+        const uint32_t usize = n - at < kGzMember ? (uint32_t)(n - at) : kGzMember;
+        const uint64_t begin = size_part[m / kTextScanTile] + size_excl[m];       // (the same in every lane, and left in vector registers: addresses of stores)
+        const uint64_t end = m + 1 == n_members ? body : size_part[(m + 1) / kTextScanTile] + size_excl[m + 1];
+        gz_emit_member(in + at, usize, meta + m, out + begin, (uint32_t)(end - begin), E);
+        if (member_end && wave_leader()) member_end[m] = end;
+    }
+    if (eof && text_wave() == 0) {
+        for (uint32_t i = TGSF_WCOOP_BEGIN(text_lane()); i < kGzEofBytes; i += TGSF_WCOOP_STRIDE) out[body + i] = gz_eof_byte(i);
+        if (member_end && wave_leader()) member_end[n_members] = total;
+    }
+}
+
+// bad_crc: the lowest member whose inflated bytes do not have the CRC32 of its trailer (0xFFFFFFFF, set by the caller: none)
+TGSF_KERNEL TGSF_BOUNDS(kTextThreads, 2) k_bgzf_crc(const uint8_t* __restrict__ gz, const tgsf_text_bgzf_block* __restrict__ blocks,
+                                                    uint32_t n_blocks, const uint8_t* __restrict__ inflated,
+                                                    const uint32_t* __restrict__ crc_tab, uint32_t* bad_crc)
+{
+    TGSF_SHARED GzCrcTables T;
+    gz_crc_tables(T, crc_tab);
+    const uint64_t n_waves = gridDim.x * (uint64_t)blockDim.x / kTextLanes;
+    uint32_t bad = 0xFFFFFFFFu;
+    for (uint64_t b = wave_uniform64(text_wave()); b < n_blocks; b += n_waves) {
+        const uint64_t trailer = wave_uniform64(blocks[b].payload) + wave_first(blocks[b].clen), at = wave_uniform64(blocks[b].out);
+        const uint32_t usize = wave_first(blocks[b].usize);
+        const uint32_t crc = gz_crc_wave<false>(T, inflated + at, usize, nullptr);
+        if (crc != wave_first(bam_le32(gz + trailer)) && (uint32_t)b < bad) bad = (uint32_t)b;
+    }
+    wave_min_into(bad_crc, bad);
 }
 
 }  // namespace tgsf

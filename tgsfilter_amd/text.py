@@ -12,6 +12,10 @@
     data, gz_summary = tx.inflate(gz)                   # inflated on the device (bgzip'ed FASTQ / FASTA lands in the text buffer)
     at, skip = tx.bgzf_bam_start(gz)                    # where a .bam file's records begin, as a BGZF virtual offset
     clean, rec_end, out_summary, s = tx.bgzf_bam_filter(ctx, gz[at:], skip)   # compressed BAM in, clean text out; s["next_gz"], s["next_skip"] resume
+    tx.reserve_bgzf_out(max_in_bytes, max_gz_bytes)     # once; then text deflated on the device into BGZF members:
+    gz, member_end, gz_summary = tx.deflate(text)       # gzip.decompress(gz) == text
+    gz, gz_summary, out_summary, s = tx.bgzf_bam_filter_bgzf(ctx, gz[at:], skip)   # compressed BAM in, compressed clean text out
+    bad_block, bad_crc = tx.verify(gz)                  # the opt-in CRC32 check of input members, on the device
 
 There is no CPU fallback: the library found beside this file must be the HIP build.  (tests/emul builds a serial
 emulation of the same kernels; only tests pass its path in.)
@@ -44,7 +48,10 @@ SYMBOLS = [
     "tgsf_text_bam_submit", "tgsf_text_bam_filter",
     "tgsf_text_bgzf_walk", "tgsf_text_bgzf_reserve", "tgsf_text_bgzf_inflate", "tgsf_text_bgzf_inflate_device",
     "tgsf_text_bam_walk_device", "tgsf_text_bgzf_bam_decode", "tgsf_text_bgzf_bam_submit", "tgsf_text_bgzf_bam_filter",
+    "tgsf_text_bgzf_bound", "tgsf_text_bgzf_out_reserve", "tgsf_text_bgzf_deflate", "tgsf_text_bgzf_deflate_device",
+    "tgsf_text_bgzf_crc_device", "tgsf_text_bgzf_verify", "tgsf_text_filter_bgzf", "tgsf_text_bam_filter_bgzf", "tgsf_text_bgzf_bam_filter_bgzf",
 ]
+BGZF_MEMBER = 0xFF00
 
 
 class Summary(C.Structure):
@@ -109,7 +116,17 @@ class BgzfBamSummary(C.Structure):
         return {"gz": self.gz.as_dict(), "bam": self.bam.as_dict(), "next_gz": self.next_gz, "next_skip": self.next_skip, "reserved": self.reserved}
 
 
-NO_BAD_QUAL = NO_BAD_BLOCK = 0xFFFFFFFF
+class GzOutSummary(C.Structure):
+    _fields_ = [("in_bytes", C.c_uint64), ("n_bytes", C.c_uint64), ("n_members", C.c_uint32), ("stored", C.c_uint32), ("stop", C.c_uint32),
+                ("device_ms", C.c_float), ("reserved", C.c_uint64)]
+
+    def as_dict(self):
+        return {"in_bytes": self.in_bytes, "n_bytes": self.n_bytes, "n_members": self.n_members, "stored": self.stored, "stop": self.stop,
+                "device_ms": self.device_ms, "reserved": self.reserved}
+
+
+NO_BAD_QUAL = NO_BAD_BLOCK = NO_BAD_CRC = 0xFFFFFFFF
+assert C.sizeof(GzOutSummary) == 40
 assert C.sizeof(BgzfBamSummary) == 104
 assert C.sizeof(BgzfBlock) == 24 == BGZF_BLOCK_DTYPE.itemsize
 assert C.sizeof(BgzfSummary) == 40
@@ -168,6 +185,19 @@ def load(path: str | None = None):
         L.tgsf_text_bgzf_bam_submit.argtypes = [vp, vp, vp, u64, u32, i, C.POINTER(IndexArrays), C.POINTER(BgzfBamSummary), C.POINTER(abi.BatchOut)]
         L.tgsf_text_bgzf_bam_filter.argtypes = [vp, vp, vp, u64, u32, i, i, vp, u64, vp, C.POINTER(OutSummary), C.POINTER(BgzfBamSummary),
                                                 C.POINTER(IndexArrays), C.POINTER(abi.BatchOut)]
+        L.tgsf_text_bgzf_bound.argtypes = [u64, i]
+        L.tgsf_text_bgzf_bound.restype = u64
+        L.tgsf_text_bgzf_out_reserve.argtypes = [vp, u64, u64]
+        L.tgsf_text_bgzf_deflate.argtypes = [vp, vp, u64, i, vp, u64, vp, C.POINTER(GzOutSummary)]
+        L.tgsf_text_bgzf_deflate_device.argtypes = [vp, vp, u64, i, vp, u64, vp, vp, vp]
+        L.tgsf_text_bgzf_crc_device.argtypes = [vp, vp, vp, u32, vp, vp, vp]
+        L.tgsf_text_bgzf_verify.argtypes = [vp, vp, u64, i, C.POINTER(u32), C.POINTER(u32)]
+        L.tgsf_text_filter_bgzf.argtypes = [vp, vp, vp, u64, i, i, i, vp, u64, C.POINTER(OutSummary), C.POINTER(Summary),
+                                            C.POINTER(IndexArrays), C.POINTER(abi.BatchOut), i, C.POINTER(GzOutSummary)]
+        L.tgsf_text_bam_filter_bgzf.argtypes = [vp, vp, vp, u64, i, i, vp, u64, C.POINTER(OutSummary), C.POINTER(BamSummary),
+                                                C.POINTER(IndexArrays), C.POINTER(abi.BatchOut), i, C.POINTER(GzOutSummary)]
+        L.tgsf_text_bgzf_bam_filter_bgzf.argtypes = [vp, vp, vp, u64, u32, i, i, vp, u64, C.POINTER(OutSummary), C.POINTER(BgzfBamSummary),
+                                                     C.POINTER(IndexArrays), C.POINTER(abi.BatchOut), i, C.POINTER(GzOutSummary)]
         if L.tgsf_text_abi_version() != ABI_VERSION:
             raise RuntimeError("libtgsf_text ABI version mismatch")
         _LIBS[path] = L
@@ -219,6 +249,11 @@ def bgzf_walk(gz, max_blocks: int, max_out_bytes: int = (1 << 64) - 1, final=Tru
     if rc != 0:
         raise TgsfError(rc, L.tgsf_text_last_error(None).decode())
     return blocks[:n.value].copy(), stop.value, consumed.value, out_bytes.value
+
+
+def bgzf_bound(n_bytes: int, eof=True, lib_path: str | None = None) -> int:
+    """Room enough for the BGZF members of any n_bytes of text (with eof: and the EOF member)."""
+    return load(lib_path).tgsf_text_bgzf_bound(int(n_bytes), int(eof))
 
 
 class TextIndexer:
@@ -502,3 +537,94 @@ class TextIndexer:
         b = _as_u8(gz)
         return self._filter(lambda *a: self.lib.tgsf_text_bgzf_bam_filter(self.h, ctx.h, b.ctypes.data, b.size, int(skip), int(final), int(fastq_out), *a),
                             BgzfBamSummary(), out, out_capacity, frag_capacity, b.size // 12, want_results, True)
+
+    # ---- the BGZF output side: text in, compressed members out; the CRC32 of input members ----------------------------------
+    def reserve_bgzf_out(self, max_in_bytes, max_gz_bytes=None):
+        """Once, before the first deflate: room for texts of up to max_in_bytes and max_gz_bytes compressed bytes (None: the
+        bound for max_in_bytes, which fits every text)."""
+        if max_gz_bytes is None:
+            max_gz_bytes = bgzf_bound(max_in_bytes, True, self.lib_path)
+        self._chk(self.lib.tgsf_text_bgzf_out_reserve(self.h, int(max_in_bytes), int(max_gz_bytes)))
+        self.max_gz_in, self.max_gz_out = int(max_in_bytes), int(max_gz_bytes)
+
+    def _gz_out(self, out, out_capacity):
+        if out is None:
+            out = np.empty(max(getattr(self, "max_gz_out", 0) if out_capacity is None else int(out_capacity), 1), np.uint8)
+        return out, (out.size if out_capacity is None else int(out_capacity))
+
+    def deflate(self, text, eof=True, out=None, out_capacity=None):
+        """Text held in host memory as BGZF members: (the compressed bytes, member_end as uint64 array, summary dict).
+        TGSF_TEXT_CAPACITY raises TgsfError(-4); its `summary` attribute says what is needed."""
+        t = _as_u8(text)
+        out, cap = self._gz_out(out, out_capacity)
+        member_end = np.zeros(t.size // BGZF_MEMBER + 2, np.uint64)
+        s = GzOutSummary()
+        self._chk(self.lib.tgsf_text_bgzf_deflate(self.h, t.ctypes.data, t.size, int(eof), out.ctypes.data, cap, member_end.ctypes.data, C.byref(s)), s)
+        return out[:s.n_bytes].tobytes(), member_end[:s.n_members].copy(), s.as_dict()
+
+    def deflate_device(self, n_bytes, eof=True, d_in=None, d_out=None, out_capacity=0, d_member_end=None, d_summary=None, stream=None):
+        """Enqueue the deflate of text already in HBM without waiting; None: the object's own output buffer as the last
+        format left it, the object's own compressed buffer and summary."""
+        self._chk(self.lib.tgsf_text_bgzf_deflate_device(self.h, d_in, int(n_bytes), int(eof), d_out, int(out_capacity), d_member_end, d_summary, stream))
+
+    def crc_device(self, blocks, d_bad_crc, d_gz=None, d_inflated=None, stream=None):
+        """Enqueue the CRC32 check of inflated members (blocks: bgzf_walk()'s table; None: the object's compressed bytes, its
+        text buffer) without waiting; the lowest mismatching member goes to the device word d_bad_crc."""
+        blocks = np.ascontiguousarray(blocks, dtype=BGZF_BLOCK_DTYPE)
+        self._chk(self.lib.tgsf_text_bgzf_crc_device(self.h, d_gz, blocks.ctypes.data if blocks.size else None, blocks.size, d_inflated, d_bad_crc, stream))
+
+    def verify(self, gz, final=True):
+        """Inflate a chunk of BGZF members into the object's text buffer and check every member's CRC32 on the device:
+        (NO_BAD_BLOCK, NO_BAD_CRC) when all is well, else TgsfError(-6) with the attributes bad_block and bad_crc."""
+        b = _as_u8(gz)
+        bb, bc = C.c_uint32(), C.c_uint32()
+        rc = self.lib.tgsf_text_bgzf_verify(self.h, b.ctypes.data, b.size, int(final), C.byref(bb), C.byref(bc))
+        if rc != 0:
+            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            e.bad_block, e.bad_crc = bb.value, bc.value
+            raise e
+        return bb.value, bc.value
+
+    def _filter_bgzf(self, call, si, eof, out, out_capacity, frag_capacity, expected_frags, want_results, in_summary_on_error, want_gz_summary):
+        """The three *_filter_bgzf calls: call(out, out_capacity, out_summary, in_summary, out_index, batch_out, eof, gz_summary)
+        is the library's; si its empty input summary."""
+        out, cap = self._gz_out(out, out_capacity)
+        so, sg = OutSummary(), GzOutSummary()
+        reads, frags, bo = self._results(frag_capacity, expected_frags) if want_results else (None, None, None)
+        rc = call(out.ctypes.data, cap, C.byref(so), C.byref(si), None, C.byref(bo) if want_results else None, int(eof),
+                  C.byref(sg) if want_gz_summary else None)
+        if rc != 0:
+            e = TgsfError(rc, self.lib.tgsf_text_last_error(self.h).decode())
+            e.summary, e.gz_summary = so.as_dict(), sg.as_dict()
+            if in_summary_on_error:
+                e.in_summary = si.as_dict()
+            raise e
+        n = sg.n_bytes if want_gz_summary else cap
+        res = (out[:n].tobytes(), sg.as_dict() if want_gz_summary else None, so.as_dict(), si.as_dict())
+        if want_results:
+            res += (reads[:si.n_records].copy(), frags[:bo.n_frags].copy())
+        return res
+
+    def filter_bgzf(self, ctx, text, fasta=False, final=True, fastq_out=None, eof=True, out=None, out_capacity=None, frag_capacity=None,
+                    want_results=False, want_gz_summary=True):
+        """Text in, compressed clean text out: (the BGZF bytes, gz summary dict, out summary dict of the text, in summary dict).
+        Without want_gz_summary the library is handed a null gz_summary and the whole buffer comes back."""
+        t = _as_u8(text)
+        if fastq_out is None:
+            fastq_out = not fasta
+        return self._filter_bgzf(lambda *a: self.lib.tgsf_text_filter_bgzf(self.h, ctx.h, t.ctypes.data, t.size, int(fasta), int(final), int(fastq_out), *a),
+                                 Summary(), eof, out, out_capacity, frag_capacity, t.size // 100, want_results, False, want_gz_summary)
+
+    def bam_filter_bgzf(self, ctx, bam, final=True, fastq_out=True, eof=True, out=None, out_capacity=None, frag_capacity=None, want_results=False,
+                        want_gz_summary=True):
+        """BAM in, compressed clean text out: as filter_bgzf()."""
+        b = _as_u8(bam)
+        return self._filter_bgzf(lambda *a: self.lib.tgsf_text_bam_filter_bgzf(self.h, ctx.h, b.ctypes.data, b.size, int(final), int(fastq_out), *a),
+                                 BamSummary(), eof, out, out_capacity, frag_capacity, b.size // 50, want_results, True, want_gz_summary)
+
+    def bgzf_bam_filter_bgzf(self, ctx, gz, skip=0, final=True, fastq_out=True, eof=True, out=None, out_capacity=None, frag_capacity=None,
+                             want_results=False, want_gz_summary=True):
+        """Compressed BAM in, compressed clean text out: as filter_bgzf()."""
+        b = _as_u8(gz)
+        return self._filter_bgzf(lambda *a: self.lib.tgsf_text_bgzf_bam_filter_bgzf(self.h, ctx.h, b.ctypes.data, b.size, int(skip), int(final), int(fastq_out), *a),
+                                 BgzfBamSummary(), eof, out, out_capacity, frag_capacity, b.size // 12, want_results, True, want_gz_summary)
