@@ -500,6 +500,15 @@ int tgsf_text_bgzf_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, u
  *     complete prefix code of at most 15 bits over the bytes that occur and symbol 256 (two codes of one bit when one byte
  *     value occurs), whose distance code is two codes of one bit, and whose code-length code is constant; or one stored block
  *     whenever the dynamic block would not be smaller.  So no payload exceeds its input by more than 5 bytes, and
+ *   - What this build writes at level 1 (tgsf_text_bgzf_out_level; level 0, the default, is the above): still one block per
+ *     member, the smallest of three -- a dynamic block of literals and matches, the level-0 dynamic block, one stored block
+ *     -- so no member is larger than at level 0.  The smallest match has 3 bytes at distance 1 and 4 bytes at any other
+ *     distance; lengths go to 258 and distances to 32768.  A match's source lies inside the member: no distance reaches in
+ *     front of the member's first byte, so every member still inflates on its own; and no byte at or behind the member's end
+ *     is read for it, so none influences its bytes.  The literal/length code is a complete prefix code of at most 15 bits
+ *     over up to 286 symbols, the distance code one over up to 30 (no or one distance in use: two codes of one bit), the
+ *     code-length code the same constant one (the run-length symbols 16, 17, 18 are not used).  The parse is a function of
+ *     the member's bytes alone, whatever the order in which the lanes of a wave arrive.
  *   - THE BOUND: tgsf_text_bgzf_bound(n_bytes, eof) = n_bytes + 31 * ceil(n_bytes / TGSF_TEXT_BGZF_MEMBER) + (eof ? 28 : 0)
  *     is room enough for every input.
  *   - Members begin at any byte address of the output.  No byte outside [out, out + summary.n_bytes) is written.  When
@@ -529,11 +538,22 @@ uint64_t tgsf_text_bgzf_bound(uint64_t n_bytes, int eof);
 
 /*
  * Once, before the first deflate: a staging buffer for inputs of up to max_in_bytes (the host form's), the object's own
- * compressed buffer of max_gz_bytes, per-member scratch (1 KiB a member).  No later call allocates.  A deflate before it is
- * TGSF_E_INVALID, a second call is TGSF_E_INVALID, an input of n_bytes > max_in_bytes TGSF_E_CAPACITY before anything is
- * copied or enqueued.
+ * compressed buffer of max_gz_bytes, per-member scratch (1 KiB a member; at level 1, below, 1280 bytes more).  No later call
+ * allocates.  A deflate before it is TGSF_E_INVALID, a second call is TGSF_E_INVALID, an input of n_bytes > max_in_bytes
+ * TGSF_E_CAPACITY before anything is copied or enqueued.
  */
 int tgsf_text_bgzf_out_reserve(tgsf_text* tx, uint64_t max_in_bytes, uint64_t max_gz_bytes);
+
+/*
+ * The coder of every deflate of the object, the composed *_filter_bgzf calls included: 0, Huffman-only (the default: the
+ * bytes of a build without this call), or 1, the match search of THE RULE.  Only BEFORE tgsf_text_bgzf_out_reserve, which
+ * sizes the scratch: level 1 adds 1280 bytes a member (the two codes of the block of matches; the parse itself is not kept,
+ * the second pass repeats it).  After the reserve, for any other level and for a null tx: TGSF_E_INVALID, and the object
+ * goes on as it was.  tgsf_text_bgzf_bound and tgsf_text_gzout_summary do not depend on the level.
+ */
+int tgsf_text_bgzf_out_level(tgsf_text* tx, int level);
+/* The level in force; TGSF_E_INVALID for a null tx. */
+int tgsf_text_bgzf_out_level_get(const tgsf_text* tx);
 
 /*
  * Everything is in HBM; the work is enqueued on `hip_stream` (NULL: the object's own) and nothing is waited for.  d_in NULL:

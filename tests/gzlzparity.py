@@ -1,0 +1,340 @@
+"""Shared checks of the match search, level 1 of the BGZF output side of libtgsf_text (include/tgsf_text.h,
+tgsf_text_bgzf_out_level): a backend (the HIP build on the GPU box, the serial emulation of the same kernels elsewhere) with
+the level set before the reserve.  Every output still goes through all of gzoutparity.Deflater.run -- gzip.decompress, the
+model's per-member inflate, the strict walk, two calls with identical bytes, canaries, the device inflate and its CRC check;
+what is new here looks at the sizes and, through the DEFLATE reader of tests/gzlzmodel.py, at the tokens.
+tests/test_gzlz_emul.py and tests/test_gzlz_gpu.py run them."""
+from __future__ import annotations
+
+import ctypes as C
+import threading
+
+import numpy as np
+
+from tests import bamparity as bp, bgzfmodel as gm, gzlzmodel as lm, gzoutmodel as zm, gzoutparity as zp, hostmodel, textoutparity as top, textparity
+from tgsfilter_amd import capi, text as tgtext
+
+MEMBER = zm.MEMBER
+_refused = zp._refused
+NEW_SYMBOLS = ("tgsf_text_bgzf_out_level", "tgsf_text_bgzf_out_level_get")
+
+
+class Deflater(zp.Deflater):
+    """gzoutparity.Deflater with the level set before the reserve (its constructor, and that one line); run() is its own."""
+
+    def __init__(self, text_lib, dev, max_in=1 << 20, level=1):
+        self.dev, self.lib = dev, text_lib
+        self.max_in = max_in
+        self.room = zm.bound(max_in, True)
+        self.tx = tgtext.TextIndexer(0, max(max_in, 64), 16, text_lib)
+        if level is not None:
+            self.tx.set_bgzf_level(level)
+        self.tx.reserve_bgzf_out(max_in, self.room)
+        self.tx.reserve_bgzf(self.room, max_in // MEMBER + 2)
+        assert self.tx.bgzf_level == (level or 0)
+
+
+def sizes_of(text, D):
+    """Through all of run(): the bytes, the members' sizes, the summary."""
+    gz, ends, s, _ = D.run(text, False, ("level", D.tx.bgzf_level, len(text), bytes(text[:12])))
+    return gz, lm.member_sizes(ends), s
+
+
+# ---- the texts of this suite -------------------------------------------------------------------------------------------------------
+LENGTHS = (3, 4, 5, 10, 11, 12, 18, 19, 34, 35, 66, 67, 130, 131, 257, 258, 259, 600)
+DISTANCES = (1, 2, 3, 4, 63, 64, 65, 127, 128, 129, 255, 256, 257, 4095, 4096, 4097, 32767, 32768)
+# With the distances above alone no match could have a distance symbol of 1, 2, 3, 8, 9 or 12 extra bits (distances 5 .. 32,
+# 513 .. 2048, 8193 .. 16384): the coverage the geometry check asks for needs these as well.
+MORE_DISTANCES = (6, 12, 24, 700, 1500, 12000)
+# where the copy begins: on, one before and one after a multiple of 64 that is none of 1024, and of 1024
+PLACES = (192, 191, 193, 1024, 1023, 1025)
+
+
+def _reps(dist):
+    """One short copy saves less than the larger header of a block of matches costs: the text repeats it, while it stays a member."""
+    return 6 if dist <= 1024 else 3 if dist <= 8192 else 1
+
+
+def geometry_texts():
+    """(what, text): noise over all 256 byte values, then a copy of `length` bytes from `dist` back (dist < length: a pattern
+    of period dist), several times over where the distance is short.  Every length with two distances, every distance with two lengths, the places taken in turn; copies
+    that end on the member's last byte; copies that are a whole member behind one member of noise; a copy whose only source
+    is 32769 back; one byte value a member long; members of 1 .. 8 bytes and of MEMBER - 3 .. MEMBER."""
+    rng = np.random.default_rng(520)
+    pairs = []
+    for i, length in enumerate(LENGTHS):
+        pairs += [(length, DISTANCES[i]), (length, 4096 if DISTANCES[i] != 4096 else 700)]
+    for dist in DISTANCES + MORE_DISTANCES:
+        pairs += [(600, dist), (35, dist)]
+    out = []
+    for k, (length, dist) in enumerate(pairs):
+        place = PLACES[k % len(PLACES)]
+        out.append((("copy", length, dist, "at", place), lm.copies_text(rng, length, dist, place, _reps(dist)) + lm.noise(rng, (k % 3) * 7)))
+    for length, dist in ((258, 1), (131, 64), (600, 4097), (259, 32768), (19, 12000), (4, 4), (3, 1)):
+        out.append((("copy to the member's end", length, dist), lm.copy_text(rng, MEMBER - length, length, dist)))
+    for length, dist in ((600, 1), (600, 3), (600, 600), (1025, 32768), (MEMBER, 64)):
+        out.append((("copy as a whole member", length, dist), lm.copy_text(rng, MEMBER, length, dist)))
+    out.append((("the only source 32769 back",), lm.copy_text(rng, 32769, 600, 32769, after=50)))
+    out.append((("one byte value",), b"~" * MEMBER))
+    fq = lm.hifi_like(rng, MEMBER)
+    for n in (1, 2, 3, 4, 5, 6, 7, 8, MEMBER - 3, MEMBER - 2, MEMBER - 1, MEMBER):
+        out.append((("hifi-like of", n), fq[:n]))
+        if n <= 8:
+            out.append((("one byte value of", n), b"A" * n))
+            out.append((("a member and", n), lm.noise(rng, MEMBER - 5) + b"ACGTA" + b"ACGTACGT"[:n]))
+    return out
+
+
+def hifi_text():
+    return lm.hifi_like(np.random.default_rng(1), 4 * MEMBER)
+
+
+def far_text():
+    return lm.three_copies(np.random.default_rng(521))
+
+
+def independence_texts():
+    rng = np.random.default_rng(522)
+    period = lm.noise(rng, 1000)
+    periodic = (period * (2 * MEMBER // 1000 + 2))[:2 * MEMBER + 1]
+    a = lm.hifi_like(rng, MEMBER)
+    x, y = lm.hifi_like(rng, 3000), a[-3000:]                          # (y: member 1 repeats member 0's end -- nothing member 0 may know of)
+    assert x != y
+    return periodic, a + x, a + y
+
+
+def fuzz_texts(seed, count, max_size=3 * MEMBER):
+    """The distributions of gzoutparity.fuzz: length, alphabet size and skew drawn the same way."""
+    rng = np.random.default_rng(seed)
+    for i in range(count):
+        n = int(rng.integers(1, max_size + 1)) if i % 4 else int(rng.integers(1, 300))
+        k = int(rng.integers(1, 257))
+        skew = float(rng.choice([0.0, 0.3, 1.0, 2.5]))
+        w = 1.0 / np.arange(1, k + 1) ** skew
+        syms = rng.permutation(256)[:k].astype(np.uint8)
+        yield ("fuzz", seed, i, n, k, skew), syms[rng.choice(k, n, p=w / w.sum())].tobytes()
+
+
+def suite_texts():
+    p, ax, ay = independence_texts()
+    return geometry_texts() + [(("hifi_like",), hifi_text()), (("three copies",), far_text()), (("period 1000",), p), (("A + X",), ax), (("A + Y",), ay)]
+
+
+# ---- 1: the interface ------------------------------------------------------------------------------------------------------------
+def interface(text_lib, dev, golden_dir):
+    L = tgtext.load(text_lib)
+    for sym in NEW_SYMBOLS:
+        assert sym in tgtext.SYMBOLS
+        getattr(L, sym)
+    assert L.tgsf_text_abi_version() == tgtext.ABI_VERSION == 2
+    assert L.tgsf_text_bgzf_out_level(None, 0) == -1 and L.tgsf_text_bgzf_out_level(None, 1) == -1 and L.tgsf_text_bgzf_out_level_get(None) == -1
+    rng = np.random.default_rng(523)
+    fq = zm.fastq_like(rng, 2 * MEMBER + 1)
+    texts = [fq[:n] for n in zp.LENGTHS] + [b"G" * n for n in zp.LENGTHS[1:]] + [zp.golden_text(golden_dir, "hifi_auto")]
+    never = Deflater(text_lib, dev, max(len(t) for t in texts), level=None)        # an object that never calls the setter
+    zero = Deflater(text_lib, dev, max(len(t) for t in texts), level=0)
+    tx = tgtext.TextIndexer(0, 1 << 17, 16, text_lib)
+    try:
+        assert never.tx.bgzf_level == 0 and zero.tx.bgzf_level == 0 and tx.bgzf_level == 0     # the default
+        for level in (-1, 2, 3, 1 << 20):
+            assert "level" in _refused(-1, tx.set_bgzf_level, level)
+            assert tx.bgzf_level == 0
+        tx.set_bgzf_level(1)
+        assert tx.bgzf_level == 1
+        tx.set_bgzf_level(0)                                               # before the reserve it may be set again
+        tx.set_bgzf_level(1)
+        tx.reserve_bgzf_out(1 << 17)
+        for level in (0, 1, 2):
+            assert ("level" if level == 2 else "reserve") in _refused(-1, tx.set_bgzf_level, level)     # after the reserve: refused, the level stays
+            assert tx.bgzf_level == 1
+        text = lm.hifi_like(rng, MEMBER + 99)
+        gz, ends, s = tx.deflate(text)                                     # the object still works, at the level it had
+        zm.check(text, gz, True, ends, s, "after the refusals")
+        assert len(gz) < len(zero.tx.deflate(text)[0])
+        for level in (0, 1):
+            assert "reserve" in _refused(-1, zero.tx.set_bgzf_level, level) and zero.tx.bgzf_level == 0
+        for t in texts:                                                    # level 0: the bytes of an object that never set a level
+            a = never.run(t, len(t) % 2 == 0, ("never set", len(t)))
+            b = zero.run(t, len(t) % 2 == 0, ("level 0", len(t)))
+            assert a[0] == b[0] and np.array_equal(a[1], b[1]) and a[3] == b[3], ("level 0 differs", len(t))
+            summary = tgtext.GzOutSummary()
+            assert b[2]["reserved"] == 0 and C.sizeof(summary) == 40
+        for n in (1, MEMBER, 5 * MEMBER + 7):                              # the bound does not know the level
+            assert tgtext.bgzf_bound(n, True, text_lib) == zm.bound(n, True)
+    finally:
+        tx.close()
+        never.close()
+        zero.close()
+
+
+# ---- 2: the size where it matters ---------------------------------------------------------------------------------------------------
+def hifi_size(text_lib, dev):
+    """At most 1.05 times what zlib level 1 writes for the same cuts: what a host's gz writer buys, with the margin the
+    project gives one block a member with a flat header (gzoutparity.golden_size)."""
+    text = hifi_text()
+    D = Deflater(text_lib, dev, len(text))
+    try:
+        gz, _, _ = sizes_of(text, D)
+        z1, z6, ho = lm.zlib_size(text, 1), lm.zlib_size(text, 6), zm.huffman_only_size(text)
+        print("hifi_like: %d bytes of text, level 1 %d, zlib level 1 %d (ratio %.4f), zlib level 6 %d (ratio %.4f), Z_HUFFMAN_ONLY %d (ratio %.4f)" % (
+            len(text), len(gz), z1, len(gz) / z1, z6, len(gz) / z6, ho, len(gz) / ho))
+        assert len(gz) <= 1.05 * z1, (len(gz), z1, len(gz) / z1)
+    finally:
+        D.close()
+
+
+# ---- 3: far matches -------------------------------------------------------------------------------------------------------------------
+def far_matches(text_lib, dev):
+    text = far_text()
+    D1, D0 = Deflater(text_lib, dev, len(text)), Deflater(text_lib, dev, len(text), level=0)
+    try:
+        g1, g0 = sizes_of(text, D1)[0], sizes_of(text, D0)[0]
+        print("three copies of 20000 random bytes over 64 values: level 0 %d, level 1 %d, ratio %.4f" % (len(g0), len(g1), len(g1) / len(g0)))
+        assert len(g1) < 0.5 * len(g0), (len(g1), len(g0))
+    finally:
+        D1.close()
+        D0.close()
+
+
+# ---- 4: never worse -------------------------------------------------------------------------------------------------------------------
+def never_worse(text_lib, dev, golden_dir, fuzz_seed=6101, fuzz_count=40):
+    texts = [((name,), zp.golden_text(golden_dir, name)) for name in zp.GOLDEN_TEXTS] + list(fuzz_texts(fuzz_seed, fuzz_count)) + suite_texts()
+    rng = np.random.default_rng(524)
+    uniform = [(("uniformly random", n), lm.uniform(rng, n)) for n in (MEMBER, 2 * MEMBER + 700)]
+    room = max(len(t) for _, t in texts + uniform)
+    D1, D0 = Deflater(text_lib, dev, room), Deflater(text_lib, dev, room, level=0)
+    smaller = 0
+    try:
+        for what, text in texts + uniform:
+            s1, s0 = sizes_of(text, D1), sizes_of(text, D0)
+            assert len(s1[1]) == len(s0[1]) and all(a <= b for a, b in zip(s1[1], s0[1])), (what, "a member is larger at level 1", s1[1], s0[1])
+            assert s1[2]["stored"] <= s0[2]["stored"], (what, s1[2], s0[2])
+            smaller += len(s1[0]) < len(s0[0])
+            if what[0] == "uniformly random":
+                assert s1[2]["stored"] == s0[2]["stored"] == len(s0[1]), (what, s1[2], s0[2])
+        assert smaller >= 20, smaller
+    finally:
+        D1.close()
+        D0.close()
+
+
+# ---- 5: match geometry ----------------------------------------------------------------------------------------------------------------
+def match_geometry(text_lib, dev):
+    texts = geometry_texts()
+    D1, D0 = Deflater(text_lib, dev, max(len(t) for _, t in texts)), Deflater(text_lib, dev, MEMBER, level=0)
+    lengths, dists = set(), set()
+    try:
+        for what, text in texts:
+            gz, sizes, _ = sizes_of(text, D1)
+            for toks in lm.member_tokens(text, gz):                        # (checks that they expand to the member's input)
+                for t in toks:
+                    if isinstance(t, tuple):
+                        lengths.add(t[0])
+                        dists.add(t[1])
+            if what == ("one byte value",):
+                g0 = sizes_of(text, D0)[0]
+                assert len(g0) - zm.FRAME > MEMBER // 8 > len(gz), (what, len(g0), len(gz))
+                assert sizes[0] < 400, (what, sizes)                       # chains of 258: 254 matches and a header
+        print("match geometry: %d texts, %d lengths %d..%d, %d distances %d..%d" % (len(texts), len(lengths), min(lengths), max(lengths), len(dists), min(dists), max(dists)))
+        assert 258 in lengths and 1 in dists and 32768 in dists, (sorted(lengths)[-3:], sorted(dists)[:3], sorted(dists)[-3:])
+        assert max(dists) <= 32768 and min(lengths) >= 3 and max(lengths) <= 258
+        assert {lm.length_extra_bits(x) for x in lengths} >= set(range(6)), sorted({lm.length_extra_bits(x) for x in lengths})
+        assert {lm.distance_extra_bits(x) for x in dists} >= set(range(14)), sorted({lm.distance_extra_bits(x) for x in dists})
+    finally:
+        D1.close()
+        D0.close()
+
+
+# ---- 6: member independence -----------------------------------------------------------------------------------------------------------
+def independence(text_lib, dev):
+    periodic, ax, ay = independence_texts()
+    D = Deflater(text_lib, dev, len(periodic))
+    try:
+        gz, sizes, _ = sizes_of(periodic, D)                               # (the model inflates every member on its own)
+        assert len(sizes) == 3 and sizes[0] < MEMBER // 20 and sizes[1] < MEMBER // 20, sizes
+        for toks, (lo, hi) in zip(lm.member_tokens(periodic, gz), zm.cuts(len(periodic))):
+            assert any(isinstance(t, tuple) for t in toks) or hi - lo < 4
+        gx, sx, _ = sizes_of(ax, D)
+        gy, sy, _ = sizes_of(ay, D)
+        assert sx[0] == sy[0] and gx[:sx[0]] == gy[:sy[0]] and gx[sx[0]:] != gy[sy[0]:], "member 0 depends on the bytes behind its end"
+    finally:
+        D.close()
+
+
+# ---- 8: the composed calls at level 1 ---------------------------------------------------------------------------------------------------
+def golden_filter_bgzf(lib, text_lib, golden_dir, name="hifi_auto"):
+    """gzoutparity.golden_filter_bgzf with the level set: gunzipped, the output is the reference's output file byte for byte."""
+    case = hostmodel.GoldenCase(golden_dir, name)
+    text = textparity.fastq_of(case.reads)
+    p = case.params()
+    p.max_batch_reads = len(case.reads)
+    p.max_batch_bases = 2 * len(text) + 64 * len(case.reads) + 4096
+    p.max_read_len = max(len(r[1]) for r in case.reads)
+    ctx = capi.Context(p, 0, lib)
+    tx = [tgtext.TextIndexer(0, len(text), len(case.reads), text_lib) for _ in range(2)]
+    try:
+        fr = top.frag_room(len(text), len(case.reads))
+        sizes = []
+        for level, t in enumerate(tx):
+            t.reserve_output(fr, top.out_room(len(text), fr))
+            t.set_bgzf_level(level)
+            t.reserve_bgzf_out(top.out_room(len(text), fr))
+            for eof in (True, False):
+                gz, sg, so, si = t.filter_bgzf(ctx, text, eof=eof)
+                assert si["n_records"] == len(case.reads) and si["stop"] == zp.END
+                zp._gz_agrees(case.ref_out, gz, sg, so, eof, (name, level, eof))
+            sizes.append(len(gz))
+        print("filter_bgzf %s: %d bytes of text, level 0 %d, level 1 %d" % (name, len(case.ref_out), sizes[0], sizes[1]))
+        assert sizes[1] <= sizes[0] and len(case.ref_out) > 1000
+    finally:
+        for t in tx:
+            t.close()
+        ctx.close()
+
+
+def golden_bam_bgzf(lib, text_lib, dev, golden_dir, name="hifi_bam"):
+    """tests/golden/<name>.in.bam as it is on disk through bgzf_bam_filter_bgzf at level 1."""
+    import os
+    case, at, chunk, m = bp.golden_model(golden_dir, name)
+    on_disk = open(os.path.join(golden_dir, name + ".in.bam"), "rb").read()
+    n = m["n_records"]
+    D = bp.Decoder(text_lib, dev, len(case.bam), n)
+    D.tx.reserve_bgzf(len(on_disk), len(gm.walk(on_disk)[0]))
+    fr = top.frag_room(m["text_bytes"], n)
+    D.tx.reserve_output(fr, top.out_room(m["text_bytes"], fr))
+    D.tx.set_bgzf_level(1)
+    D.tx.reserve_bgzf_out(top.out_room(m["text_bytes"], fr))
+    ctx = capi.Context(bp.golden_params(case, m), 0, lib)
+    try:
+        goff, skip = D.tx.bgzf_bam_start(on_disk)
+        gz, sg, so, si = D.tx.bgzf_bam_filter_bgzf(ctx, on_disk[goff:], skip)
+        assert si["bam"]["n_records"] == n and si["gz"]["bad_block"] == zp.NONE and D.tx.bgzf_level == 1
+        zp._gz_agrees(case.ref_out, gz, sg, so, True, (name, "bgzf bam, level 1"))
+        assert len(case.ref_out) > 1000
+    finally:
+        ctx.close()
+        D.close()
+
+
+# ---- 9: two objects, levels 0 and 1, on two threads -----------------------------------------------------------------------------------
+def two_levels_two_threads(text_lib, make_dev):
+    errors = []
+    texts = [t for _, t in fuzz_texts(6102, 8, max_size=2 * MEMBER)] + [hifi_text()[:2 * MEMBER + 5], far_text()]
+
+    def work(level):
+        try:
+            D = Deflater(text_lib, make_dev(), max(len(t) for t in texts), level=level)
+            try:
+                for t in texts:
+                    sizes_of(t, D)
+            finally:
+                D.close()
+        except BaseException as e:              # noqa: BLE001 -- reported by the asserting thread
+            errors.append((level, repr(e)))
+
+    th = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    assert not errors, errors

@@ -79,7 +79,9 @@ struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exa
     uint32_t max_zmembers = 0;
     uint8_t* d_zin = nullptr;           // max_zin rounded up to 16
     uint8_t* d_zout = nullptr;          // max_zout rounded up to 16
+    int zlevel = 0;                     // tgsf_text_bgzf_out_level: 0 Huffman-only, 1 the match search
     GzMeta* d_zmeta = nullptr;          // codes, CRC32 and verdict of every member
+    GzLzMeta* d_zlz = nullptr;          // level 1: whether the block of matches won, and its two codes
     uint64_t* d_zsize = nullptr;        // the members' sizes -> exclusive sums within blocks of kTextScanTile members
     uint64_t* d_zsize_part = nullptr;   // ... and the blocks' offsets
     uint64_t* d_zend = nullptr;         // the byte behind each member (the host form's member_end)
@@ -1166,6 +1168,18 @@ extern "C" uint64_t tgsf_text_bgzf_bound(uint64_t n_bytes, int eof)
     return n_bytes > UINT64_MAX - extra ? UINT64_MAX : n_bytes + extra;
 }
 
+extern "C" int tgsf_text_bgzf_out_level(tgsf_text* tx, int level)
+{
+    if (!tx) return TGSF_E_INVALID;
+    if (level != 0 && level != 1) return fail(tx, TGSF_E_INVALID, "level is 0 (Huffman-only) or 1 (the match search), not %d", level);
+    if (tx->zout_reserved)
+        return fail(tx, TGSF_E_INVALID, "tgsf_text_bgzf_out_reserve has been called already: the level (%d) sizes its scratch and is set before it", tx->zlevel);
+    tx->zlevel = level;
+    return TGSF_OK;
+}
+
+extern "C" int tgsf_text_bgzf_out_level_get(const tgsf_text* tx) { return tx ? tx->zlevel : TGSF_E_INVALID; }
+
 extern "C" int tgsf_text_bgzf_out_reserve(tgsf_text* tx, uint64_t max_in_bytes, uint64_t max_gz_bytes)
 {
     if (!tx) return TGSF_E_INVALID;
@@ -1179,6 +1193,7 @@ extern "C" int tgsf_text_bgzf_out_reserve(tgsf_text* tx, uint64_t max_in_bytes, 
     e |= dev_alloc(tx, &tx->d_zin, (max_in_bytes + 15u) & ~15ull);
     if (!e) e |= dev_alloc(tx, &tx->d_zout, (max_gz_bytes + 15u) & ~15ull);
     if (!e) e |= dev_alloc(tx, &tx->d_zmeta, (size_t)members);
+    if (!e && tx->zlevel) e |= dev_alloc(tx, &tx->d_zlz, (size_t)members);
     if (!e) e |= dev_alloc(tx, &tx->d_zsize, (size_t)members + 1);
     if (!e) e |= dev_alloc(tx, &tx->d_zsize_part, (size_t)members / kTextScanTile + 2);
     if (!e) e |= dev_alloc(tx, &tx->d_zend, (size_t)members + 1);
@@ -1215,13 +1230,20 @@ static int enqueue_gzout(tgsf_text* tx, const uint8_t* d_in, uint64_t n, int eof
     const int he = rt_memset(S, 0, sizeof *S, st);
     if (he) return fail(tx, TGSF_E_HIP, "device memset failed: %s", rt_errstr(he));
     if (tx->profile) (void)rt_event_record(tx->zev[0], st);
+    // level 1: a wave per member as well, two waves a workgroup (a table a wave: LDS)
+    const unsigned glz = grid_cap(std::min(std::max(blocks_for((uint64_t)members * kTextLanes, kLzThreads), 1u), 4096u));
     if (members) {
-        TGSF_LAUNCH(k_gz_count, g, kTextThreads, st, d_in, n, members, (const uint32_t*)tx->d_crc_tab, tx->d_zmeta, tx->d_zsize, S);
+        if (tx->zlevel) TGSF_LAUNCH(k_gz_count_lz, glz, kLzThreads, st, d_in, n, members, (const uint32_t*)tx->d_crc_tab, tx->d_zmeta, tx->d_zlz, tx->d_zsize, S);
+        else TGSF_LAUNCH(k_gz_count, g, kTextThreads, st, d_in, n, members, (const uint32_t*)tx->d_crc_tab, tx->d_zmeta, tx->d_zsize, S);
         TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_zsize, (uint64_t)members, tx->d_zsize_part);
     }
     TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_zsize_part, nb, &S->total);
-    TGSF_LAUNCH(k_gz_emit, g, kTextThreads, st, d_in, n, members, eof, (const GzMeta*)tx->d_zmeta, (const uint64_t*)tx->d_zsize,
-                (const uint64_t*)tx->d_zsize_part, (const GzState*)S, capacity, d_out, d_member_end, d_summary);
+    if (tx->zlevel)
+        TGSF_LAUNCH(k_gz_emit_lz, glz, kLzThreads, st, d_in, n, members, eof, (const GzMeta*)tx->d_zmeta, (const GzLzMeta*)tx->d_zlz, (const uint64_t*)tx->d_zsize,
+                    (const uint64_t*)tx->d_zsize_part, (const GzState*)S, capacity, d_out, d_member_end, d_summary);
+    else
+        TGSF_LAUNCH(k_gz_emit, g, kTextThreads, st, d_in, n, members, eof, (const GzMeta*)tx->d_zmeta, (const uint64_t*)tx->d_zsize,
+                    (const uint64_t*)tx->d_zsize_part, (const GzState*)S, capacity, d_out, d_member_end, d_summary);
     if (tx->profile) { (void)rt_event_record(tx->zev[1], st); tx->zev_recorded = true; }
     if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
     return TGSF_OK;

@@ -50,6 +50,7 @@ SYMBOLS = [
     "tgsf_text_bam_walk_device", "tgsf_text_bgzf_bam_decode", "tgsf_text_bgzf_bam_submit", "tgsf_text_bgzf_bam_filter",
     "tgsf_text_bgzf_bound", "tgsf_text_bgzf_out_reserve", "tgsf_text_bgzf_deflate", "tgsf_text_bgzf_deflate_device",
     "tgsf_text_bgzf_crc_device", "tgsf_text_bgzf_verify", "tgsf_text_filter_bgzf", "tgsf_text_bam_filter_bgzf", "tgsf_text_bgzf_bam_filter_bgzf",
+    "tgsf_text_bgzf_out_level", "tgsf_text_bgzf_out_level_get",
 ]
 BGZF_MEMBER = 0xFF00
 
@@ -188,6 +189,8 @@ def load(path: str | None = None):
         L.tgsf_text_bgzf_bound.argtypes = [u64, i]
         L.tgsf_text_bgzf_bound.restype = u64
         L.tgsf_text_bgzf_out_reserve.argtypes = [vp, u64, u64]
+        L.tgsf_text_bgzf_out_level.argtypes = [vp, i]
+        L.tgsf_text_bgzf_out_level_get.argtypes = [vp]
         L.tgsf_text_bgzf_deflate.argtypes = [vp, vp, u64, i, vp, u64, vp, C.POINTER(GzOutSummary)]
         L.tgsf_text_bgzf_deflate_device.argtypes = [vp, vp, u64, i, vp, u64, vp, vp, vp]
         L.tgsf_text_bgzf_crc_device.argtypes = [vp, vp, vp, u32, vp, vp, vp]
@@ -546,6 +549,15 @@ class TextIndexer:
             max_gz_bytes = bgzf_bound(max_in_bytes, True, self.lib_path)
         self._chk(self.lib.tgsf_text_bgzf_out_reserve(self.h, int(max_in_bytes), int(max_gz_bytes)))
         self.max_gz_in, self.max_gz_out = int(max_in_bytes), int(max_gz_bytes)
+
+    def set_bgzf_level(self, level):
+        """Before reserve_bgzf_out: 0, the Huffman-only coder (the default), or 1, the match search.  Holds for every deflate of
+        the object, the composed *_filter_bgzf calls included."""
+        self._chk(self.lib.tgsf_text_bgzf_out_level(self.h, int(level)))
+
+    @property
+    def bgzf_level(self):
+        return int(self.lib.tgsf_text_bgzf_out_level_get(self.h))
 
     def _gz_out(self, out, out_capacity):
         if out is None:

@@ -2,11 +2,15 @@
 """Times the BGZF output side of libtgsf_text on the GPU: the deflate of a chunk of FASTQ text as the format
 stage leaves it in the object's output buffer (k_gz_count, the scan, k_gz_emit), beside that format's own stage times for
 the same text; k_bgzf_crc on the members tools/text_bgzf_measure.py inflates; and zlib with Z_HUFFMAN_ONLY and at level 1 on
-one CPU thread over the same text, all of it.  Each GPU figure is the median of --reps calls, by a host clock around a call that ends in
+one CPU thread over the same text, all of it (--zlib-members: its first members; 0: none).  --level sets the coder (0: Huffman-only, 1: the match search; with it
+zlib at level 6 is timed too), --text the text: synth, the HiFi-like reads of tgsfilter_amd/synth.py as the goldens have
+them (random bases, Gaussian qualities), or hifi_like, tests/gzlzmodel.py's (qualities in runs, names with a long common
+prefix).  Each GPU figure is the median of --reps calls, by a host clock around a call that ends in
 a synchronise, after one warm-up call; device_ms is the kernels alone, by HIP events.  Prints one JSON line; --out writes it
 to a file too.
 
     python tools/text_gzout_measure.py --members 4096 --reps 7 --out gzout_measure.json
+    python tools/text_gzout_measure.py --members 4096 --reps 7 --level 1 --text hifi_like
 """
 import argparse
 import gzip
@@ -21,7 +25,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from tests import bgzfmodel as gm, gzoutmodel as zm, textoutparity as top, textparity  # noqa: E402
+from tests import bgzfmodel as gm, gzlzmodel as lm, gzoutmodel as zm, textoutparity as top, textparity  # noqa: E402
 from tgsfilter_amd import abi, synth, text as tgtext  # noqa: E402
 from tools.text_bgzf_measure import median_ms, records  # noqa: E402
 
@@ -39,22 +43,31 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--members", type=int, default=4096, help="members of 0xFF00 bytes of text to deflate, and of BAM to check")
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--level", type=int, default=0, choices=(0, 1), help="tgsf_text_bgzf_out_level")
+    ap.add_argument("--text", default="synth", choices=("synth", "hifi_like"))
+    ap.add_argument("--zlib-members", type=int, default=None, help="members zlib is timed on (default: all of the text; 0: none)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import torch
     dev = torch.device("cuda", 0)
     rng = np.random.default_rng(7)
-    res = {"members": a.members, "reps": a.reps}
+    res = {"members": a.members, "reps": a.reps, "level": a.level, "text": a.text}
 
     # HiFi-like reads as the goldens have them, as many as fill the members; the format of all of them whole leaves the text
     # in the object's output buffer, which is where the deflate takes it from
     want = a.members * zm.MEMBER
-    reads = synth.make_reads(11, min(max(want // 30000, 4), 256), "hifi", mean_len=15000, zoo=False)
-    text = textparity.fastq_of(reads)                                   # (a few MB of different reads, repeated)
+    if a.text == "synth":
+        reads = synth.make_reads(11, min(max(want // 30000, 4), 256), "hifi", mean_len=15000, zoo=False)
+        text = textparity.fastq_of(reads)                               # (a few MB of different reads, repeated)
+    else:
+        text = lm.hifi_like(np.random.default_rng(1), min(want, 64 * zm.MEMBER) + 5000)
+        text = text[:text.rfind(b"\n@") + 1]
     while len(text) < want:
         text += text
     text = text[:text.rfind(b"\n@", 0, want) + 1]
-    tx = tgtext.TextIndexer(0, len(text), len(text) // 2000 + 16, None)
+    tx = tgtext.TextIndexer(0, len(text), len(text) // 1500 + 16, None)
+    if a.level:
+        tx.set_bgzf_level(a.level)
     idx, s = tx.index(text)
     n = s["n_records"]
     assert s["stop"] == tgtext.END and s["consumed"] == len(text) and n > 0
@@ -80,9 +93,13 @@ def main():
                       "kernels_text_GB_per_s": len(text) / sg["device_ms"] / 1e6 if sg["device_ms"] else None,
                       "note": "call time: memset, k_gz_count, two scan launches, k_gz_emit, one synchronise; device_ms: the same by HIP events"}
     tx.close()
-    for key, level, strategy in (("zlib_huffman_only_one_thread", 6, zlib.Z_HUFFMAN_ONLY), ("zlib_level_1_one_thread", 1, zlib.Z_DEFAULT_STRATEGY)):
-        rate, share = zlib_rate(text, level, strategy)
-        res[key] = {"text_GB_per_s": rate, "share": share}
+    ztext = text if a.zlib_members is None else text[:a.zlib_members * zm.MEMBER]
+    coders = [("zlib_huffman_only_one_thread", 6, zlib.Z_HUFFMAN_ONLY), ("zlib_level_1_one_thread", 1, zlib.Z_DEFAULT_STRATEGY)]
+    if a.level:
+        coders.append(("zlib_level_6_one_thread", 6, zlib.Z_DEFAULT_STRATEGY))
+    for key, level, strategy in coders if ztext else []:
+        rate, share = zlib_rate(ztext, level, strategy)
+        res[key] = {"text_GB_per_s": rate, "share": share, "text_bytes": len(ztext)}
 
     # the CRC check on the members of tools/text_bgzf_measure.py: 64 different members of 0xFF00 inflated bytes, repeated
     pool = records(rng, 15000, 64 * 0xFF00)
