@@ -3,10 +3,17 @@ tgsf_text_bgzf_out_level): a backend (the HIP build on the GPU box, the serial e
 the level set before the reserve.  Every output still goes through all of gzoutparity.Deflater.run -- gzip.decompress, the
 model's per-member inflate, the strict walk, two calls with identical bytes, canaries, the device inflate and its CRC check;
 what is new here looks at the sizes and, through the DEFLATE reader of tests/gzlzmodel.py, at the tokens.
-tests/test_gzlz_emul.py and tests/test_gzlz_gpu.py run them."""
+tests/test_gzlz_emul.py and tests/test_gzlz_gpu.py run them.
+
+include/tgsf_text.h leaves the compressed bytes unspecified; tests/golden/gz_bytes_pinned.json pins them all the same (pinned_bytes,
+below), so that a change that means to keep them is seen to.  A change that means to alter them regenerates the file, from the
+emulation built from its own sources -- `python -m tests.gzlzparity` -- and says so."""
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
+import os
 import threading
 
 import numpy as np
@@ -338,3 +345,56 @@ def two_levels_two_threads(text_lib, make_dev):
     for t in th:
         t.join()
     assert not errors, errors
+
+
+# ---- 10: the compressed bytes, pinned ---------------------------------------------------------------------------------------------------
+def pinned_texts():
+    """(what, text, eof): small texts that between them take every path of both levels -- no member, a member of one byte, a
+    member that is exactly full and one byte more, a tail behind whole members, a stored member, runs of 258 at distance 1, and a
+    block repeated 33 000 bytes on (its only source lies just behind the window of 32 768, and the members' seam cuts the copy);
+    and, with and without the EOF member, a block repeated 32 700 bytes on: matches at the far end of the window, inside the member.
+    Half with the EOF member, none over three members."""
+    fq = zm.fastq_like(np.random.default_rng(530), MEMBER + 1)
+    block = bytes(np.random.default_rng(533).integers(0, 64, 33000).astype(np.uint8))
+    near = bytes(np.random.default_rng(534).integers(0, 64, 32700).astype(np.uint8))
+    return [("empty", b"", True),
+            ("one byte", b"A", False),
+            ("fastq_like, a full member", fq[:MEMBER], True),
+            ("fastq_like, a full member and a byte", fq[:MEMBER + 1], False),
+            ("hifi_like, two members and 700 bytes", lm.hifi_like(np.random.default_rng(531), 2 * MEMBER + 700)[:2 * MEMBER + 700], True),
+            ("3000 random bytes", lm.uniform(np.random.default_rng(532), 3000), False),
+            ("70000 bytes of one value", b"~" * 70000, True),
+            ("33000 bytes over 64 values, twice", block + block, False),
+            ("32700 bytes over 64 values, twice", near + near, True),
+            ("32700 bytes over 64 values, twice, no EOF member", near + near, False)]
+
+
+def pinned_digests(text_lib, dev):
+    """{"level L: what": the SHA-256 of what TextIndexer.deflate(text, eof) returns at level L}"""
+    texts = pinned_texts()
+    assert sum(eof for _, _, eof in texts) * 2 == len(texts) and all(len(t) <= 3 * MEMBER for _, t, _ in texts)
+    out = {}
+    for level in (0, 1):
+        D = Deflater(text_lib, dev, max(len(t) for _, t, _ in texts), level=level)
+        try:
+            for what, text, eof in texts:
+                out["level %d: %s" % (level, what)] = hashlib.sha256(D.tx.deflate(text, eof)[0]).hexdigest()
+        finally:
+            D.close()
+    return out
+
+
+def pinned_bytes(text_lib, dev, golden_dir):
+    with open(os.path.join(golden_dir, "gz_bytes_pinned.json")) as f:
+        want = json.load(f)["sha256"]
+    got = pinned_digests(text_lib, dev)
+    assert got == want, ("the compressed bytes differ from tests/golden/gz_bytes_pinned.json", sorted(k for k in set(got) | set(want) if got.get(k) != want.get(k)))
+
+
+if __name__ == "__main__":                                                # regenerate the pin from the emulation as it is built now
+    here = os.path.dirname(os.path.abspath(__file__))
+    digests = pinned_digests(os.path.join(here, "emul", "libtgsf_text_emul.so"), zp.HostMem())
+    with open(os.path.join(here, "golden", "gz_bytes_pinned.json"), "w") as f:
+        json.dump({"what": "SHA-256 of TextIndexer.deflate(text, eof) for tests.gzlzparity.pinned_texts()", "sha256": digests}, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("wrote %d digests" % len(digests))

@@ -81,6 +81,10 @@ def test_golden_bam_bgzf_at_level_1(libs, golden_dir):
     lp.golden_bam_bgzf(libs[0], libs[1], zp.HostMem(), golden_dir, "hifi_bam")
 
 
+def test_compressed_bytes_are_the_pinned_ones(tlib, golden_dir):
+    lp.pinned_bytes(tlib, zp.HostMem(), golden_dir)
+
+
 def test_two_levels_two_threads(tlib):
     lp.two_levels_two_threads(tlib, zp.HostMem)
 

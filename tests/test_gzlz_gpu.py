@@ -64,3 +64,7 @@ def test_gpu_golden_filter_bgzf_at_level_1(golden_dir):
 
 def test_gpu_golden_bam_bgzf_at_level_1(golden_dir):
     lp.golden_bam_bgzf(None, None, zp.TorchMem(own_stream=False), golden_dir, "hifi_bam")
+
+
+def test_gpu_compressed_bytes_are_the_pinned_ones(golden_dir):
+    lp.pinned_bytes(None, zp.TorchMem(own_stream=False), golden_dir)

@@ -15,6 +15,22 @@ namespace tgsf_emul { thread_local Dim3 threadIdx, blockIdx, blockDim, gridDim; 
 
 using namespace tgsf;
 
+// an event pair around the launches of a call (profile): begin() and end() record on the launches' stream; ms() once that stream
+// has been waited for, the milliseconds between them -- 0 when profiling is off, nothing was recorded, or it has been read
+struct Span {
+    rt_event e[2] = {nullptr, nullptr};
+    bool recorded = false;
+    void begin(rt_stream st) { (void)rt_event_record(e[0], st); }
+    void end(rt_stream st) { (void)rt_event_record(e[1], st); recorded = true; }
+    float ms(bool profile)
+    {
+        float t = 0.0f;
+        if (profile && recorded && !rt_event_ms(&t, e[0], e[1])) { recorded = false; return t; }
+        (void)rt_last_error();
+        return 0.0f;
+    }
+};
+
 struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exact, the text has TGSF_TEXT_PAD)
     uint64_t max_bytes, max_pieces;
     uint32_t max_records;
@@ -87,11 +103,9 @@ struct tgsf_text : rt_ctx {                // (alloc_slack 0: the arrays are exa
     uint64_t* d_zend = nullptr;         // the byte behind each member (the host form's member_end)
     GzState* d_zstate = nullptr;
     tgsf_text_gzout_summary* d_zsummary = nullptr;
-    rt_event zev[2] = {nullptr, nullptr};
-    bool zev_recorded = false;
+    Span zev;
     // around the last index, and around the stages of the last format (profile)
-    rt_event ev[2] = {nullptr, nullptr};
-    bool ev_recorded = false;
+    Span ev;
     rt_event oev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool oev_recorded = false;
 };
@@ -105,9 +119,9 @@ extern "C" void tgsf_text_destroy(tgsf_text* tx)
     if (!tx) return;
     (void)rt_set_device(tx->device);
     if (tx->stream) { (void)rt_sync(tx->stream); rt_stream_destroy(tx->stream); }
-    for (rt_event e : tx->ev) rt_event_destroy(e);
+    for (rt_event e : tx->ev.e) rt_event_destroy(e);
     for (rt_event e : tx->oev) rt_event_destroy(e);
-    for (rt_event e : tx->zev) rt_event_destroy(e);
+    for (rt_event e : tx->zev.e) rt_event_destroy(e);
     dev_free_all(tx);
     delete tx;
 }
@@ -129,7 +143,7 @@ extern "C" int tgsf_text_create(int device, uint64_t max_bytes, uint32_t max_rec
     tx->stream = nullptr;
     if (rt_set_device(device)) { delete tx; return fail(nullptr, TGSF_E_NO_DEVICE, "hipSetDevice(%d) failed: no usable HIP device (there is no CPU fallback)", device); }
     if (rt_stream_create(&tx->stream)) { delete tx; return fail(nullptr, TGSF_E_HIP, "stream creation failed"); }
-    for (rt_event& e : tx->ev) if (rt_event_create(&e)) { tgsf_text_destroy(tx); return fail(nullptr, TGSF_E_HIP, "event creation failed"); }
+    for (rt_event& e : tx->ev.e) if (rt_event_create(&e)) { tgsf_text_destroy(tx); return fail(nullptr, TGSF_E_HIP, "event creation failed"); }
     const uint64_t text_bytes = ((max_bytes + 15u) & ~15ull) + TGSF_TEXT_PAD;
     int e = 0;
     e |= dev_alloc(tx, &tx->d_text, text_bytes);
@@ -175,6 +189,32 @@ extern "C" int tgsf_text_buffers(tgsf_text* tx, tgsf_text_device_buffers* out)
 }
 
 static unsigned blocks_for(uint64_t items, unsigned per_block) { return (unsigned)((items + per_block - 1) / per_block); }
+// the grid of a kernel whose waves stride over `waves` items: a wave each, at most a few per SIMD of the device
+static unsigned wave_grid(uint64_t waves, unsigned threads = kTextThreads, unsigned cap = 2048u)
+{
+    return grid_cap(std::min(std::max(blocks_for(waves * kTextLanes, threads), 1u), cap));
+}
+// what every enqueue ends with
+static int launched(tgsf_text* tx) { return rt_last_error() ? fail(tx, TGSF_E_HIP, "kernel launch failed") : TGSF_OK; }
+// a caller's stream (NULL: the object's own)
+static rt_stream stream_of(tgsf_text* tx, void* hip_stream) { return hip_stream ? (rt_stream)hip_stream : tx->stream; }
+
+// bytes from the device to the host on the object's stream (0: no copy), which is then waited for; wait = false: a copy
+// follows on the same stream, and its wait is this one's
+static int down(tgsf_text* tx, void* dst, const void* src, size_t bytes, bool wait = true)
+{
+    int he = bytes ? rt_d2h(dst, src, bytes, tx->stream) : 0;
+    if (!he && wait) he = rt_sync(tx->stream);
+    return he ? fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he)) : TGSF_OK;
+}
+
+// exclusive prefix sums of a[0 .. n) on st, in place and two levels deep (part: the blocks' offsets; *total: the sum)
+template <typename T> static void enqueue_scan(rt_stream st, T* a, uint64_t n, uint64_t* part, uint64_t* total)
+{
+    const uint32_t nb = (uint32_t)((n + kTextScanTile - 1) / kTextScanTile);
+    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles<T>, nb, 256, st, a, n, part);
+    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, part, nb, total);
+}
 
 // the seven launches of one index, on st; nothing is waited for
 static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int fasta, int final,
@@ -187,7 +227,7 @@ static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int f
     const unsigned gemit = blocks_for((pieces + kTextEmitPieces - 1) / kTextEmitPieces * kTextLanes, kTextThreads);
     const unsigned gsmall = grid_cap(std::min(blocks_for(tx->max_records, kTextThreads), 2048u));
     const unsigned gfold = std::min(gsmall, 64u);                                  // every wave ends in two atomics on one word each
-    if (tx->profile) (void)rt_event_record(tx->ev[0], st);
+    if (tx->profile) tx->ev.begin(st);
     if (pieces) {
         TGSF_LAUNCH(k_text_mark, gwave, kTextThreads, st, d_text, n, pieces, (uint16_t*)tx->d_bits, tx->d_cnt);
         TGSF_LAUNCH_COOP(k_text_scan_tiles<uint32_t>, nb, 256, st, tx->d_cnt, pieces, tx->d_part);
@@ -199,18 +239,8 @@ static int enqueue_index(tgsf_text* tx, const uint8_t* d_text, uint64_t n, int f
     TGSF_LAUNCH(k_text_check, gsmall, kTextThreads, st, d_text, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, tx->d_state, I);
     TGSF_LAUNCH(k_text_fold<TextState>, gfold, kTextThreads, st, (const uint32_t*)I.len, tx->max_records, fasta, tx->d_state);
     TGSF_LAUNCH_COOP(k_text_finish, 1, 64, st, n, fasta, final, (const uint64_t*)tx->d_table, tx->max_records, (const TextState*)tx->d_state, d_summary);
-    if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-    return TGSF_OK;
-}
-
-// milliseconds between the events around the last index; the stream has been synchronised
-static float index_ms(tgsf_text* tx)
-{
-    float ms = 0.0f;
-    if (tx->profile && tx->ev_recorded && !rt_event_ms(&ms, tx->ev[0], tx->ev[1])) { tx->ev_recorded = false; return ms; }
-    (void)rt_last_error();
-    return 0.0f;
+    if (tx->profile) tx->ev.end(st);
+    return launched(tx);
 }
 
 static int check_args(tgsf_text* tx, uint64_t n_bytes, int fasta, int final)
@@ -260,32 +290,29 @@ extern "C" int tgsf_text_index_device(tgsf_text* tx, const uint8_t* d_text, uint
     if ((e = check_index(tx, d_index))) return e;
     (void)rt_set_device(tx->device);
     return enqueue_index(tx, d_text, n_bytes, fasta, final, d_index ? *d_index : tx->d_index, d_summary ? d_summary : tx->d_summary,
-                         hip_stream ? (rt_stream)hip_stream : tx->stream);
+                         stream_of(tx, hip_stream));
 }
 
 // the first k entries of the object's own index to the host, on the object's stream, which is waited for
 static int fetch_index(tgsf_text* tx, const tgsf_text_index_arrays* out_index, size_t k)
 {
     if (!out_index || !k) return TGSF_OK;
-    int he = 0;
-    if (out_index->seq_off) he |= rt_d2h(out_index->seq_off, tx->d_index.seq_off, k * 8, tx->stream);
-    if (out_index->qual_off) he |= rt_d2h(out_index->qual_off, tx->d_index.qual_off, k * 8, tx->stream);
-    if (out_index->len) he |= rt_d2h(out_index->len, tx->d_index.len, k * 4, tx->stream);
-    if (out_index->name_off) he |= rt_d2h(out_index->name_off, tx->d_index.name_off, k * 8, tx->stream);
-    if (out_index->name_len) he |= rt_d2h(out_index->name_len, tx->d_index.name_len, k * 4, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    return he ? fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he)) : TGSF_OK;
+    const tgsf_text_index_arrays &O = *out_index, &D = tx->d_index;   // (an array the caller does not take: 0 bytes)
+    int e = down(tx, O.seq_off, D.seq_off, O.seq_off ? k * 8 : 0, false);
+    if (!e) e = down(tx, O.qual_off, D.qual_off, O.qual_off ? k * 8 : 0, false);
+    if (!e) e = down(tx, O.len, D.len, O.len ? k * 4 : 0, false);
+    if (!e) e = down(tx, O.name_off, D.name_off, O.name_off ? k * 8 : 0, false);
+    if (!e) e = down(tx, O.name_len, D.name_len, O.name_len ? k * 4 : 0);
+    return e;
 }
 
 // the object's own summary and index to the host; the copies run on the object's stream, which is waited for
 static int fetch(tgsf_text* tx, const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_text_summary* sum)
 {
-    int he = rt_d2h(sum, tx->d_summary, sizeof *sum, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    sum->device_ms = index_ms(tx);
-    const int e = fetch_index(tx, out_index, sum->n_records);
+    int e = down(tx, sum, tx->d_summary, sizeof *sum);
     if (e) return e;
+    sum->device_ms = tx->ev.ms(tx->profile);
+    if ((e = fetch_index(tx, out_index, sum->n_records))) return e;
     if (out_summary) *out_summary = *sum;
     return TGSF_OK;
 }
@@ -339,15 +366,10 @@ static int run_filter(tgsf_text* tx, tgsf_ctx* ctx, uint32_t n_records, uint64_t
         if (!e) e = tgsf_wait(ctx);
         if (e) return fail(tx, e, "libtgsf: %s", tgsf_last_error(ctx));
         uint32_t nf = 0;
-        int he = rt_d2h(&nf, tx->d_nfrags, 4, tx->stream);
-        if (bo) he |= rt_d2h(bo->reads, tx->d_reads, (size_t)n_records * sizeof(tgsf_read_result), tx->stream);
-        if (!he) he = rt_sync(tx->stream);
-        if (!he && nf > dout.frag_capacity) return fail(tx, TGSF_E_CAPACITY, "batch produced %u fragments, caller provided room for %u", nf, dout.frag_capacity);
-        if (!he && nf && bo && bo->frags) {
-            he = rt_d2h(bo->frags, d_fr, (size_t)nf * sizeof(tgsf_fragment), tx->stream);
-            if (!he) he = rt_sync(tx->stream);
-        }
-        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+        if ((e = down(tx, &nf, tx->d_nfrags, 4, false))) return e;
+        if ((e = down(tx, bo ? bo->reads : nullptr, tx->d_reads, bo ? (size_t)n_records * sizeof(tgsf_read_result) : 0))) return e;
+        if (nf > dout.frag_capacity) return fail(tx, TGSF_E_CAPACITY, "batch produced %u fragments, caller provided room for %u", nf, dout.frag_capacity);
+        if (nf && bo && bo->frags && (e = down(tx, bo->frags, d_fr, (size_t)nf * sizeof(tgsf_fragment)))) return e;
         if (bo) bo->n_frags = nf;
         *n_frags = nf;
     }
@@ -410,21 +432,17 @@ static int enqueue_format(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_
                           uint64_t* d_rec_end, tgsf_text_out_summary* d_summary, rt_stream st)
 {
     const uint64_t n = n_frags;
-    const uint32_t nb = (uint32_t)((n + kTextScanTile - 1) / kTextScanTile);
     const unsigned gfrag = grid_cap(std::min(std::max(blocks_for(n, kTextThreads), 1u), 2048u));
-    // a wave per 4 KiB piece of the output, as many as the capacity has, at most a few per SIMD of the device: they stride
-    const unsigned gcopy = grid_cap(std::min(std::max(blocks_for(((capacity + kTextPiece - 1) / kTextPiece) * kTextLanes, kTextThreads), 1u), 2048u));
+    const unsigned gcopy = wave_grid((capacity + kTextPiece - 1) / kTextPiece);   // a wave per 4 KiB piece of the output, as many as the capacity has
     TextOutState* S = tx->d_ostate;
     if (tx->profile) (void)rt_event_record(tx->oev[0], st);
     TGSF_LAUNCH(k_textout_flag, gfrag, kTextThreads, st, d_frags, n, tx->d_opass, S);
-    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles<uint32_t>, nb, 256, st, tx->d_opass, n, tx->d_opass_part);
-    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_opass_part, nb, &S->n_records);
+    enqueue_scan(st, tx->d_opass, n, tx->d_opass_part, &S->n_records);
     if (n)
         TGSF_LAUNCH(k_textout_size, gfrag, kTextThreads, st, d_text, I, d_reads, d_frags, n, fastq_out, (const uint32_t*)tx->d_opass,
                     (const uint64_t*)tx->d_opass_part, tx->d_osize, tx->d_ometa, S);
     if (tx->profile) (void)rt_event_record(tx->oev[1], st);
-    if (n) TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_osize, n, tx->d_osize_part);
-    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_osize_part, nb, &S->n_bytes);
+    enqueue_scan(st, tx->d_osize, n, tx->d_osize_part, &S->n_bytes);
     TGSF_LAUNCH(k_textout_finish, gfrag, kTextThreads, st, (const uint64_t*)tx->d_osize, (const uint64_t*)tx->d_osize_part,
                 (const uint32_t*)tx->d_opass, (const uint64_t*)tx->d_opass_part, (const TextOutMeta*)tx->d_ometa, n, capacity,
                 (const TextOutState*)S, tx->d_oends, d_rec_end, d_summary);
@@ -433,8 +451,7 @@ static int enqueue_format(tgsf_text* tx, const uint8_t* d_text, const tgsf_text_
         TGSF_LAUNCH(k_textout_copy, gcopy, kTextThreads, st, d_text, I, d_frags, (const TextOutMeta*)tx->d_ometa, (const uint64_t*)tx->d_oends,
                     n, fastq_out, (const TextOutState*)S, capacity, d_out);
     if (tx->profile) { (void)rt_event_record(tx->oev[3], st); tx->oev_recorded = true; }
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-    return TGSF_OK;
+    return launched(tx);
 }
 
 // milliseconds of the last format's stages; ms[3] (may be NULL); returns their sum.  The format has finished.
@@ -479,7 +496,7 @@ extern "C" int tgsf_text_format_device(tgsf_text* tx, const uint8_t* d_text, con
     if (!d_out) { d_out = tx->d_out; out_capacity = std::min(out_capacity, tx->max_out); }
     (void)rt_set_device(tx->device);
     return enqueue_format(tx, d_text ? d_text : tx->d_text, d_index ? *d_index : tx->d_index, d_reads, d_frags, n_frags, fastq_out, d_out,
-                          out_capacity, d_rec_end, d_summary ? d_summary : tx->d_osummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
+                          out_capacity, d_rec_end, d_summary ? d_summary : tx->d_osummary, stream_of(tx, hip_stream));
 }
 
 // where the format calls and the filter calls have the kept records formatted to; gz: as BGZF members (out and out_capacity are
@@ -510,9 +527,7 @@ static int format_down(tgsf_text* tx, const tgsf_read_result* d_reads, const tgs
                            tx->d_osummary, tx->stream);
     if (e) return e;
     tgsf_text_out_summary sum;
-    int he = rt_d2h(&sum, tx->d_osummary, sizeof sum, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    if ((e = down(tx, &sum, tx->d_osummary, sizeof sum))) return e;
     sum.device_ms = format_ms(tx, nullptr);
     *out_summary = sum;
     if (sum.stop == TGSF_TEXT_CAPACITY)
@@ -522,11 +537,8 @@ static int format_down(tgsf_text* tx, const tgsf_read_result* d_reads, const tgs
         if ((e = check_gzout(tx, sum.n_bytes, to.eof))) return e;
         return gzout_down(tx, tx->d_out, sum.n_bytes, to.eof, out, to.out_capacity, nullptr, to.gz_summary);
     }
-    if (sum.n_bytes) he |= rt_d2h(out, tx->d_out, (size_t)sum.n_bytes, tx->stream);
-    if (rec_end && sum.n_records) he |= rt_d2h(rec_end, tx->d_orec_end, (size_t)sum.n_records * 8, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    return TGSF_OK;
+    if ((e = down(tx, out, tx->d_out, (size_t)sum.n_bytes, false))) return e;
+    return down(tx, rec_end, tx->d_orec_end, rec_end ? (size_t)sum.n_records * 8 : 0);
 }
 
 extern "C" int tgsf_text_format(tgsf_text* tx, uint32_t n_records, int fasta, const tgsf_read_result* reads, const tgsf_fragment* frags,
@@ -636,20 +648,17 @@ static int enqueue_bam(tgsf_text* tx, const uint8_t* d_bam, const uint64_t* rec_
                        const tgsf_text_index_arrays& I, tgsf_text_bam_summary* d_summary, rt_stream st)
 {
     const uint64_t n = n_walked;
-    const uint32_t nb = (uint32_t)((n + kTextScanTile - 1) / kTextScanTile);
     const unsigned grec = grid_cap(std::min(std::max(blocks_for(n, kTextThreads), 1u), 2048u));
     const unsigned gfold = std::min(grec, 64u);                                    // every wave ends in two atomics on one word each
-    // a wave per 4 KiB piece of the text, as many as the object's buffer has, at most a few per SIMD of the device: they stride
-    const unsigned gtext = grid_cap(std::min(std::max(blocks_for(((tx->max_bytes + TGSF_TEXT_PAD + kTextPiece - 1) / kTextPiece) * kTextLanes, kTextThreads), 1u), 2048u));
+    const unsigned gtext = wave_grid((tx->max_bytes + TGSF_TEXT_PAD + kTextPiece - 1) / kTextPiece);   // a wave per 4 KiB piece of the text, as many as the object's buffer has
     const int he = rt_h2d(tx->d_brec_off, rec_off, (size_t)(n + 1) * 8, st);
     if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
     BamState* S = tx->d_bstate;
-    if (tx->profile) (void)rt_event_record(tx->ev[0], st);
+    if (tx->profile) tx->ev.begin(st);
     TGSF_LAUNCH_COOP(k_bam_reset, 1, 64, st, S);
     if (n) {
         TGSF_LAUNCH(k_bam_heads, grec, kTextThreads, st, d_bam, (const uint64_t*)tx->d_brec_off, n_walked, tx->d_bsize, tx->d_boseq, I, S);
-        TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_bsize, n, tx->d_bsize_part);
-        TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_bsize_part, nb, &S->total);
+        enqueue_scan(st, tx->d_bsize, n, tx->d_bsize_part, &S->total);
         TGSF_LAUNCH(k_bam_layout, grec, kTextThreads, st, (const uint64_t*)tx->d_bsize, (const uint64_t*)tx->d_bsize_part, n_walked, tx->max_bytes, S,
                     tx->d_bends, I);
         TGSF_LAUNCH(k_text_fold<BamState>, gfold, kTextThreads, st, (const uint32_t*)I.len, n_walked, 0, S);
@@ -657,9 +666,8 @@ static int enqueue_bam(tgsf_text* tx, const uint8_t* d_bam, const uint64_t* rec_
     TGSF_LAUNCH_COOP(k_bam_finish, 1, 64, st, (const uint64_t*)tx->d_brec_off, (const uint64_t*)tx->d_bends, n_walked, walk_stop, (const BamState*)S, d_summary);
     TGSF_LAUNCH(k_bam_unpack, gtext, kTextThreads, st, d_bam, (const uint64_t*)tx->d_brec_off, (const uint32_t*)tx->d_boseq, I,
                 (const uint64_t*)tx->d_bends, d_summary, tx->d_text);
-    if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-    return TGSF_OK;
+    if (tx->profile) tx->ev.end(st);
+    return launched(tx);
 }
 
 extern "C" int tgsf_text_bam_decode_device(tgsf_text* tx, const uint8_t* d_bam, uint64_t n_bytes, int final, const uint64_t* rec_off,
@@ -676,7 +684,7 @@ extern "C" int tgsf_text_bam_decode_device(tgsf_text* tx, const uint8_t* d_bam, 
     if ((e = check_index(tx, d_index))) return e;
     (void)rt_set_device(tx->device);
     return enqueue_bam(tx, d_bam ? d_bam : tx->d_bam, rec_off, n_walked, walk_stop, d_index ? *d_index : tx->d_index,
-                       d_summary ? d_summary : tx->d_bsummary, hip_stream ? (rt_stream)hip_stream : tx->stream);
+                       d_summary ? d_summary : tx->d_bsummary, stream_of(tx, hip_stream));
 }
 
 // the chain walk on the device, on the object's stream; one copy and one wait bring n, stop, consumed and the offsets down
@@ -685,12 +693,11 @@ static int bam_walk_down(tgsf_text* tx, const uint8_t* d_bam, uint64_t start, ui
 {
     static_assert(sizeof(BamWalkHead) == 16, "the head is two of the table's words");
     TGSF_LAUNCH_COOP(k_bam_walk, 1, 64, tx->stream, d_bam, start, n_bytes, final, tx->max_records, (BamWalkHead*)tx->d_bwalk, tx->d_bwalk + 2);
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
+    if (launched(tx)) return TGSF_E_HIP;
     // a walked record has 36 bytes or more: the head and as many offsets as the bytes can hold records, and one
     const uint64_t most = std::min<uint64_t>(tx->max_records, (n_bytes - start) / 36u);
-    int he = rt_d2h(tx->h_bwalk.data(), tx->d_bwalk, (size_t)(2 + most + 1) * 8, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+    const int e = down(tx, tx->h_bwalk.data(), tx->d_bwalk, (size_t)(2 + most + 1) * 8);
+    if (e) return e;
     BamWalkHead head;
     memcpy(&head, tx->h_bwalk.data(), sizeof head);
     memcpy(rec_off, tx->h_bwalk.data() + 2, ((size_t)head.n + 1) * 8);
@@ -714,6 +721,16 @@ extern "C" int tgsf_text_bam_walk_device(tgsf_text* tx, const uint8_t* d_bam, ui
     return bam_walk_down(tx, d_bam ? d_bam : tx->d_bam, start, n_bytes, final, rec_off, n, stop, consumed);
 }
 
+// the decode of the records walked into h_rec_off, from the object's BAM buffer, on the object's stream; the summary comes down (a wait)
+static int bam_summary_down(tgsf_text* tx, uint32_t n_walked, uint32_t walk_stop, tgsf_text_bam_summary* sum)
+{
+    int e = enqueue_bam(tx, tx->d_bam, tx->h_rec_off.data(), n_walked, walk_stop, tx->d_index, tx->d_bsummary, tx->stream);
+    if (!e) e = down(tx, sum, tx->d_bsummary, sizeof *sum);
+    if (e) return e;
+    sum->device_ms = tx->ev.ms(tx->profile);
+    return TGSF_OK;
+}
+
 // walk, upload, decode on the object's stream; the summary comes down (the one wait)
 static int bam_decode_down(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, tgsf_text_bam_summary* sum)
 {
@@ -721,14 +738,9 @@ static int bam_decode_down(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, 
     uint64_t consumed = 0;
     int e = tgsf_text_bam_walk(bam, n_bytes, final, tx->max_records, tx->h_rec_off.data(), &n_walked, &walk_stop, &consumed);
     if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
-    int he = n_bytes ? rt_h2d(tx->d_bam, bam, n_bytes, tx->stream) : 0;
+    const int he = n_bytes ? rt_h2d(tx->d_bam, bam, n_bytes, tx->stream) : 0;
     if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
-    if ((e = enqueue_bam(tx, tx->d_bam, tx->h_rec_off.data(), n_walked, walk_stop, tx->d_index, tx->d_bsummary, tx->stream))) return e;
-    he = rt_d2h(sum, tx->d_bsummary, sizeof *sum, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    sum->device_ms = index_ms(tx);
-    return TGSF_OK;
+    return bam_summary_down(tx, n_walked, walk_stop, sum);
 }
 
 extern "C" int tgsf_text_bam_decode(tgsf_text* tx, const uint8_t* bam, uint64_t n_bytes, int final, const tgsf_text_index_arrays* out_index,
@@ -755,11 +767,11 @@ static int bad_quality(tgsf_text* tx, const uint8_t* rec, const tgsf_text_bam_su
     return fail(tx, TGSF_E_DATA, "unsupported quality value in %.*s (record %u of the chunk): the filter has not run", (int)strnlen(name, r[8]), name, sum.bad_qual);
 }
 
-// ---- the one path of the four calls that run the filter: ingest, filter, format ------------------------------------------------
+// ---- the one path of the nine calls that run the filter: ingest, filter, format ------------------------------------------------
 // How the chunk gets into the object and where its summary goes.  Text (text_summary): upload and index; the caller's summary
 // is written when the call has succeeded.  BAM (bam_summary): walk, copy up, decode; the text has text_bytes bytes, the
 // caller's summary is written before the filter runs, and a quality that decodes to '\n' refuses the chunk.
-// Compressed BAM (gz_summary, with bam_summary = &gz_summary->bam): the members inflated into the object's BAM buffer, the
+// Compressed BAM (gz_summary, with bam_summary = &gz_summary->bam, which filter_call sets): the members inflated into the object's BAM buffer, the
 // chain walked there from byte `skip` on, then the decode as for BAM.
 struct Ingest {
     const uint8_t* bytes;
@@ -779,10 +791,10 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
 {
     int e;
     (void)rt_set_device(tx->device);
-    const bool down = bo && bo->frags;                                 // the caller takes the fragments: its capacity counts
-    if (down && (e = grow_frags(tx, bo))) return e;
-    tgsf_fragment* d_fr = down ? tx->d_frags : (to ? tx->d_ofrags : nullptr);
-    const uint32_t fr_cap = down ? bo->frag_capacity : (to ? tx->max_frags : 0u);
+    const bool takes = bo && bo->frags;                                // the caller takes the fragments: its capacity counts
+    if (takes && (e = grow_frags(tx, bo))) return e;
+    tgsf_fragment* d_fr = takes ? tx->d_frags : (to ? tx->d_ofrags : nullptr);
+    const uint32_t fr_cap = takes ? bo->frag_capacity : (to ? tx->max_frags : 0u);
     if (to) memset(to->out_summary, 0, sizeof *to->out_summary);
     if (to && to->gz_summary) memset(to->gz_summary, 0, sizeof *to->gz_summary);
     tgsf_text_summary ts;
@@ -801,9 +813,7 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
         if (!in.gz_summary) return bad_quality(tx, in.bytes + tx->h_rec_off[bs.bad_qual], bs);
         uint8_t rec[4 + 32 + 255] = {0};                               // the record's name is in HBM only
         const uint64_t at = tx->h_rec_off[bs.bad_qual];
-        int he = rt_d2h(rec, tx->d_bam + at, (size_t)std::min<uint64_t>(sizeof rec, in.gz_summary->gz.out_bytes - at), tx->stream);
-        if (!he) he = rt_sync(tx->stream);
-        if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
+        if ((e = down(tx, rec, tx->d_bam + at, (size_t)std::min<uint64_t>(sizeof rec, in.gz_summary->gz.out_bytes - at)))) return e;
         return bad_quality(tx, rec, bs);
     }
     uint32_t nf = 0;
@@ -817,14 +827,27 @@ static int ingest_filter_format(tgsf_text* tx, tgsf_ctx* ctx, const Ingest& in, 
     return format_down(tx, tx->d_reads, d_fr, nf, *to);
 }
 
+// The nine calls that run the filter: what they are refused for before anything is copied or enqueued -- the input's checks by
+// its kind, which the summary that is there tells; to: NULL for the submit forms, whose batch_out is not optional -- then the path.
+static int check_bgzf_bam(tgsf_text* tx, uint64_t n_bytes, int final);
+static int filter_call(tgsf_text* tx, tgsf_ctx* ctx, Ingest in, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo, const FormatTo* to)
+{
+    if (!tx) return TGSF_E_INVALID;
+    const bool no_input = !ctx || !(in.text_summary || in.bam_summary || in.gz_summary) || (!in.bytes && in.n_bytes);
+    const bool no_output = to ? !to->out_summary || (bo && !bo->reads) || (!to->out && to->out_capacity) : !bo || !bo->reads;
+    if (no_input || no_output) return fail(tx, TGSF_E_INVALID, "null argument");
+    int e = to ? check_format(tx, 0, in.fasta, to->fastq_out) : TGSF_OK;
+    if (!e) e = in.gz_summary ? check_bgzf_bam(tx, in.n_bytes, in.final) : in.bam_summary ? check_bam(tx, in.n_bytes, in.final) : check_args(tx, in.n_bytes, in.fasta, in.final);
+    if (!e && to && to->gz) e = check_gzout(tx, 0, to->eof);
+    if (e) return e;
+    if (in.gz_summary) in.bam_summary = &in.gz_summary->bam;
+    return ingest_filter_format(tx, ctx, in, out_index, bo, to);
+}
+
 extern "C" int tgsf_text_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final,
                                 const tgsf_text_index_arrays* out_index, tgsf_text_summary* out_summary, tgsf_batch_out* bo)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !bo || !bo->reads || (!text && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    const int e = check_args(tx, n_bytes, fasta, final);
-    if (e) return e;
-    return ingest_filter_format(tx, ctx, {text, n_bytes, fasta, final, out_summary, nullptr}, out_index, bo, nullptr);
+    return filter_call(tx, ctx, {text, n_bytes, fasta, final, out_summary}, out_index, bo, nullptr);
 }
 
 extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* text, uint64_t n_bytes, int fasta, int final, int fastq_out,
@@ -832,36 +855,22 @@ extern "C" int tgsf_text_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* tex
                                 tgsf_text_summary* in_summary,
                                 const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!text && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, fasta, fastq_out);
-    if (!e) e = check_args(tx, n_bytes, fasta, final);
-    if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
-    return ingest_filter_format(tx, ctx, {text, n_bytes, fasta, final, in_summary, nullptr}, out_index, bo, &to);
+    return filter_call(tx, ctx, {text, n_bytes, fasta, final, in_summary}, out_index, bo, &to);
 }
 
 extern "C" int tgsf_text_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final,
                                     const tgsf_text_index_arrays* out_index, tgsf_text_bam_summary* out_summary, tgsf_batch_out* bo)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !bo || !bo->reads || (!bam && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    const int e = check_bam(tx, n_bytes, final);
-    if (e) return e;
-    return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, out_summary}, out_index, bo, nullptr);
+    return filter_call(tx, ctx, {bam, n_bytes, 0, final, nullptr, out_summary}, out_index, bo, nullptr);
 }
 
 extern "C" int tgsf_text_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
                                     uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
                                     tgsf_text_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!bam && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, 0, fastq_out);
-    if (!e) e = check_bam(tx, n_bytes, final);
-    if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
-    return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
+    return filter_call(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
 }
 
 // ---- the BGZF input side ---------------------------------------------------------------------------------------------------
@@ -970,14 +979,12 @@ static int enqueue_bgzf(tgsf_text* tx, const uint8_t* d_gz, const tgsf_text_bgzf
     int he = n_blocks ? rt_h2d(tx->d_gblocks, blocks, (size_t)n_blocks * sizeof *blocks, st) : 0;
     if (!he) he = rt_memset(tx->d_gstate, 0xFF, sizeof(BgzfState), st);
     if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
-    // a wave per member, at most a few per SIMD of the device: they stride
-    const unsigned g = grid_cap(std::min(std::max(blocks_for((uint64_t)n_blocks * kTextLanes, kTextThreads), 1u), 2048u));
-    if (tx->profile) (void)rt_event_record(tx->ev[0], st);
+    const unsigned g = wave_grid(n_blocks);                            // a wave per member
+    if (tx->profile) tx->ev.begin(st);
     if (n_blocks) TGSF_LAUNCH(k_bgzf_inflate, g, kTextThreads, st, d_gz, (const tgsf_text_bgzf_block*)tx->d_gblocks, n_blocks, d_out, tx->d_gstate);
     TGSF_LAUNCH_COOP(k_bgzf_finish, 1, 64, st, n_blocks, walk_stop, consumed, out_bytes, (const BgzfState*)tx->d_gstate, d_summary);
-    if (tx->profile) { (void)rt_event_record(tx->ev[1], st); tx->ev_recorded = true; }
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-    return TGSF_OK;
+    if (tx->profile) tx->ev.end(st);
+    return launched(tx);
 }
 
 // a caller's table against the chunk's size and the rule's bounds: the kernels' bounds are these words.  *out: the inflated
@@ -1014,34 +1021,39 @@ extern "C" int tgsf_text_bgzf_inflate_device(tgsf_text* tx, const uint8_t* d_gz,
     if (out > out_capacity) return fail(tx, TGSF_E_CAPACITY, "the members inflate to %llu bytes, there is room for %llu", (unsigned long long)out, (unsigned long long)out_capacity);
     (void)rt_set_device(tx->device);
     return enqueue_bgzf(tx, d_gz, blocks, n_blocks, walk_stop, n_blocks ? end + 8 : 0, out, d_out, d_summary ? d_summary : tx->d_gsummary,
-                        hip_stream ? (rt_stream)hip_stream : tx->stream);
+                        stream_of(tx, hip_stream));
 }
 
-// What tgsf_text_bgzf_inflate and tgsf_text_bgzf_verify share: the walk into h_gblocks (room: inflated bytes), the refusal of a
-// first member that does not fit, the bytes up, the inflate into the text buffer enqueued on the object's stream.
+// What the calls that take compressed bytes from the host share.  gz_walk: the walk into h_gblocks (room: inflated bytes).
+// walk_up_inflate, of tgsf_text_bgzf_inflate and tgsf_text_bgzf_verify: their checks, the walk, the refusal of a first member
+// that does not fit.  up_inflate: the bytes up, the inflate into d_out enqueued on the object's stream.
 struct GzWalk { uint32_t n, stop; uint64_t consumed, out_bytes; };
+static int gz_walk(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint64_t room, GzWalk* w)
+{
+    const int e = tgsf_text_bgzf_walk(gz, n_bytes, final, tx->max_gblocks, room, tx->h_gblocks.data(), &w->n, &w->stop, &w->consumed, &w->out_bytes);
+    return e ? fail(tx, e, "the walk failed: %s", g_create_error.c_str()) : TGSF_OK;
+}
 static int walk_up_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint64_t room, GzWalk* w)
 {
     if (final != 0 && final != 1) return fail(tx, TGSF_E_INVALID, "final is 0 or 1");
     int e = check_bgzf(tx, n_bytes);
+    if (!e) e = gz_walk(tx, gz, n_bytes, final, room, w);
     if (e) return e;
-    e = tgsf_text_bgzf_walk(gz, n_bytes, final, tx->max_gblocks, room, tx->h_gblocks.data(), &w->n, &w->stop, &w->consumed, &w->out_bytes);
-    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
     if (!w->n && w->stop == TGSF_TEXT_CAPACITY)
         return fail(tx, TGSF_E_CAPACITY, "the first member does not fit: room for %llu bytes (the text buffer %llu)", (unsigned long long)room, (unsigned long long)tx->max_bytes);
     return TGSF_OK;
 }
-static int up_inflate(tgsf_text* tx, const uint8_t* gz, const GzWalk& w)
+static int up_inflate(tgsf_text* tx, const uint8_t* gz, const GzWalk& w, uint8_t* d_out)
 {
     (void)rt_set_device(tx->device);
     const int he = w.consumed ? rt_h2d(tx->d_gz, gz, w.consumed, tx->stream) : 0;
     if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
-    return enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), w.n, w.stop, w.consumed, w.out_bytes, tx->d_text, tx->d_gsummary, tx->stream);
+    return enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), w.n, w.stop, w.consumed, w.out_bytes, d_out, tx->d_gsummary, tx->stream);
 }
-static int bad_member(tgsf_text* tx, uint32_t b)
+static int bad_member(tgsf_text* tx, uint32_t b, const char* tail = "")
 {
-    return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes", b,
-                (unsigned long long)tx->h_gblocks[b].payload, tx->h_gblocks[b].usize);
+    return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes%s", b,
+                (unsigned long long)tx->h_gblocks[b].payload, tx->h_gblocks[b].usize, tail);
 }
 
 extern "C" int tgsf_text_bgzf_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t n_bytes, int final, uint8_t* out, uint64_t out_capacity,
@@ -1051,14 +1063,12 @@ extern "C" int tgsf_text_bgzf_inflate(tgsf_text* tx, const uint8_t* gz, uint64_t
     if (!out_summary || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
     GzWalk w;
     int e = walk_up_inflate(tx, gz, n_bytes, final, out ? std::min(out_capacity, tx->max_bytes) : tx->max_bytes, &w);
-    if (!e) e = up_inflate(tx, gz, w);
+    if (!e) e = up_inflate(tx, gz, w, tx->d_text);
     if (e) return e;
     tgsf_text_bgzf_summary sum;
-    int he = rt_d2h(&sum, tx->d_gsummary, sizeof sum, tx->stream);
-    if (!he && out && w.out_bytes) he = rt_d2h(out, tx->d_text, w.out_bytes, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    sum.device_ms = index_ms(tx);
+    if ((e = down(tx, &sum, tx->d_gsummary, sizeof sum, false))) return e;
+    if ((e = down(tx, out, tx->d_text, out ? w.out_bytes : 0))) return e;
+    sum.device_ms = tx->ev.ms(tx->profile);
     *out_summary = sum;
     return sum.bad_block != 0xFFFFFFFFu ? bad_member(tx, sum.bad_block) : TGSF_OK;
 }
@@ -1071,39 +1081,28 @@ static int bgzf_bam_decode_down(tgsf_text* tx, const Ingest& in, tgsf_text_bam_s
     tgsf_text_bgzf_bam_summary* S = in.gz_summary;
     memset(S, 0, sizeof *S);
     S->gz.bad_block = S->bam.bad_qual = 0xFFFFFFFFu;
-    uint32_t n = 0, gz_stop = 0;
-    uint64_t consumed = 0, out_bytes = 0;
-    int e = tgsf_text_bgzf_walk(in.bytes, in.n_bytes, in.final, tx->max_gblocks, tx->max_bam, tx->h_gblocks.data(), &n, &gz_stop, &consumed, &out_bytes);
-    if (e) return fail(tx, e, "the walk failed: %s", g_create_error.c_str());
-    S->gz.n_blocks = n; S->gz.stop = gz_stop; S->gz.consumed = consumed; S->gz.out_bytes = out_bytes;
-    if (in.skip > out_bytes)
-        return fail(tx, TGSF_E_INVALID, "skip is %u, the %u members of the chunk inflate to %llu bytes", in.skip, n, (unsigned long long)out_bytes);
-    int he = consumed ? rt_h2d(tx->d_gz, in.bytes, consumed, tx->stream) : 0;
-    if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
-    if ((e = enqueue_bgzf(tx, tx->d_gz, tx->h_gblocks.data(), n, gz_stop, consumed, out_bytes, tx->d_bam, tx->d_gsummary, tx->stream))) return e;
-    he = rt_d2h(&S->gz, tx->d_gsummary, sizeof S->gz, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    S->gz.device_ms = index_ms(tx);
-    if (S->gz.bad_block != 0xFFFFFFFFu)
-        return fail(tx, TGSF_E_DATA, "member %u of the chunk (its DEFLATE stream at byte %llu) does not inflate to its %u bytes: nothing was decoded", S->gz.bad_block,
-                    (unsigned long long)tx->h_gblocks[S->gz.bad_block].payload, tx->h_gblocks[S->gz.bad_block].usize);
+    GzWalk w;
+    int e = gz_walk(tx, in.bytes, in.n_bytes, in.final, tx->max_bam, &w);
+    if (e) return e;
+    S->gz.n_blocks = w.n; S->gz.stop = w.stop; S->gz.consumed = w.consumed; S->gz.out_bytes = w.out_bytes;
+    if (in.skip > w.out_bytes)
+        return fail(tx, TGSF_E_INVALID, "skip is %u, the %u members of the chunk inflate to %llu bytes", in.skip, w.n, (unsigned long long)w.out_bytes);
+    if ((e = up_inflate(tx, in.bytes, w, tx->d_bam))) return e;
+    if ((e = down(tx, &S->gz, tx->d_gsummary, sizeof S->gz))) return e;
+    S->gz.device_ms = tx->ev.ms(tx->profile);
+    if (S->gz.bad_block != 0xFFFFFFFFu) return bad_member(tx, S->gz.bad_block, ": nothing was decoded");
     // the records are final only when the file ends here and every byte of the chunk was inflated
-    const int rec_final = in.final && gz_stop == TGSF_TEXT_END && consumed == in.n_bytes;
+    const int rec_final = in.final && w.stop == TGSF_TEXT_END && w.consumed == in.n_bytes;
     uint32_t n_walked = 0, walk_stop = 0;
     uint64_t walked_to = 0;
-    if ((e = bam_walk_down(tx, tx->d_bam, in.skip, out_bytes, rec_final, tx->h_rec_off.data(), &n_walked, &walk_stop, &walked_to))) return e;
-    if ((e = enqueue_bam(tx, tx->d_bam, tx->h_rec_off.data(), n_walked, walk_stop, tx->d_index, tx->d_bsummary, tx->stream))) return e;
-    he = rt_d2h(bs, tx->d_bsummary, sizeof *bs, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    bs->device_ms = index_ms(tx);
+    if ((e = bam_walk_down(tx, tx->d_bam, in.skip, w.out_bytes, rec_final, tx->h_rec_off.data(), &n_walked, &walk_stop, &walked_to))) return e;
+    if ((e = bam_summary_down(tx, n_walked, walk_stop, bs))) return e;
     S->bam = *bs;
     // the virtual offset of the first record that is not indexed: the last member that begins at or in front of it holds it
-    S->next_gz = consumed;
+    S->next_gz = w.consumed;
     S->next_skip = 0;
-    if (bs->consumed < out_bytes) {
-        uint32_t lo = 0, hi = n;                                       // the first member that begins behind it
+    if (bs->consumed < w.out_bytes) {
+        uint32_t lo = 0, hi = w.n;                                     // the first member that begins behind it
         while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (tx->h_gblocks[mid].out > bs->consumed) hi = mid; else lo = mid + 1; }
         const uint32_t m = lo - 1;
         S->next_gz = m ? tx->h_gblocks[m - 1].payload + tx->h_gblocks[m - 1].clen + 8 : 0;
@@ -1111,7 +1110,7 @@ static int bgzf_bam_decode_down(tgsf_text* tx, const Ingest& in, tgsf_text_bam_s
     }
     // the members of this call were cut short by the object's room and hold no whole record, and the next call would be this
     // one again: named as what it is, a record larger than the object, instead of a chunk to be continued
-    if (gz_stop == TGSF_TEXT_CAPACITY && bs->n_records == 0 && bs->stop == TGSF_TEXT_END && S->next_gz == 0 && S->next_skip == in.skip)
+    if (w.stop == TGSF_TEXT_CAPACITY && bs->n_records == 0 && bs->stop == TGSF_TEXT_END && S->next_gz == 0 && S->next_skip == in.skip)
         bs->stop = S->bam.stop = TGSF_TEXT_CAPACITY;
     return TGSF_OK;
 }
@@ -1140,24 +1139,15 @@ extern "C" int tgsf_text_bgzf_bam_decode(tgsf_text* tx, const uint8_t* gz, uint6
 extern "C" int tgsf_text_bgzf_bam_submit(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final,
                                          const tgsf_text_index_arrays* out_index, tgsf_text_bgzf_bam_summary* out_summary, tgsf_batch_out* bo)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !bo || !bo->reads || (!gz && n_bytes)) return fail(tx, TGSF_E_INVALID, "null argument");
-    const int e = check_bgzf_bam(tx, n_bytes, final);
-    if (e) return e;
-    return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &out_summary->bam, out_summary, skip}, out_index, bo, nullptr);
+    return filter_call(tx, ctx, {gz, n_bytes, 0, final, nullptr, nullptr, out_summary, skip}, out_index, bo, nullptr);
 }
 
 extern "C" int tgsf_text_bgzf_bam_filter(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final, int fastq_out,
                                          uint8_t* out, uint64_t out_capacity, uint64_t* rec_end, tgsf_text_out_summary* out_summary,
                                          tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!gz && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, 0, fastq_out);
-    if (!e) e = check_bgzf_bam(tx, n_bytes, final);
-    if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, rec_end, out_summary};
-    return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &in_summary->bam, in_summary, skip}, out_index, bo, &to);
+    return filter_call(tx, ctx, {gz, n_bytes, 0, final, nullptr, nullptr, in_summary, skip}, out_index, bo, &to);
 }
 
 // ---- the BGZF output side: text in, compressed members out ------------------------------------------------------------------------
@@ -1188,7 +1178,7 @@ extern "C" int tgsf_text_bgzf_out_reserve(tgsf_text* tx, uint64_t max_in_bytes, 
     const uint64_t members = (max_in_bytes + kGzMember - 1) / kGzMember;
     if (members >= 0xFFFFFFFFull) return fail(tx, TGSF_E_INVALID, "max_in_bytes of %llu: more members than 32 bits count", (unsigned long long)max_in_bytes);
     (void)rt_set_device(tx->device);
-    for (rt_event& ev : tx->zev) if (!ev && rt_event_create(&ev)) return fail(tx, TGSF_E_HIP, "event creation failed");
+    for (rt_event& ev : tx->zev.e) if (!ev && rt_event_create(&ev)) return fail(tx, TGSF_E_HIP, "event creation failed");
     int e = 0;
     e |= dev_alloc(tx, &tx->d_zin, (max_in_bytes + 15u) & ~15ull);
     if (!e) e |= dev_alloc(tx, &tx->d_zout, (max_gz_bytes + 15u) & ~15ull);
@@ -1223,30 +1213,26 @@ static int enqueue_gzout(tgsf_text* tx, const uint8_t* d_in, uint64_t n, int eof
                          tgsf_text_gzout_summary* d_summary, rt_stream st)
 {
     const uint32_t members = (uint32_t)((n + kGzMember - 1) / kGzMember);
-    const uint32_t nb = (members + kTextScanTile - 1) / kTextScanTile;
-    // a wave per member, at most a few per SIMD of the device: they stride
-    const unsigned g = grid_cap(std::min(std::max(blocks_for((uint64_t)members * kTextLanes, kTextThreads), 1u), 2048u));
+    const unsigned g = wave_grid(members);                             // a wave per member
     GzState* S = tx->d_zstate;
     const int he = rt_memset(S, 0, sizeof *S, st);
     if (he) return fail(tx, TGSF_E_HIP, "device memset failed: %s", rt_errstr(he));
-    if (tx->profile) (void)rt_event_record(tx->zev[0], st);
+    if (tx->profile) tx->zev.begin(st);
     // level 1: a wave per member as well, two waves a workgroup (a table a wave: LDS)
-    const unsigned glz = grid_cap(std::min(std::max(blocks_for((uint64_t)members * kTextLanes, kLzThreads), 1u), 4096u));
+    const unsigned glz = wave_grid(members, kLzThreads, 4096u);
     if (members) {
         if (tx->zlevel) TGSF_LAUNCH(k_gz_count_lz, glz, kLzThreads, st, d_in, n, members, (const uint32_t*)tx->d_crc_tab, tx->d_zmeta, tx->d_zlz, tx->d_zsize, S);
         else TGSF_LAUNCH(k_gz_count, g, kTextThreads, st, d_in, n, members, (const uint32_t*)tx->d_crc_tab, tx->d_zmeta, tx->d_zsize, S);
-        TGSF_LAUNCH_COOP(k_text_scan_tiles<uint64_t>, nb, 256, st, tx->d_zsize, (uint64_t)members, tx->d_zsize_part);
     }
-    TGSF_LAUNCH_COOP(k_textout_scan_top, 1, 64, st, tx->d_zsize_part, nb, &S->total);
+    enqueue_scan(st, tx->d_zsize, (uint64_t)members, tx->d_zsize_part, &S->total);
     if (tx->zlevel)
         TGSF_LAUNCH(k_gz_emit_lz, glz, kLzThreads, st, d_in, n, members, eof, (const GzMeta*)tx->d_zmeta, (const GzLzMeta*)tx->d_zlz, (const uint64_t*)tx->d_zsize,
                     (const uint64_t*)tx->d_zsize_part, (const GzState*)S, capacity, d_out, d_member_end, d_summary);
     else
         TGSF_LAUNCH(k_gz_emit, g, kTextThreads, st, d_in, n, members, eof, (const GzMeta*)tx->d_zmeta, (const uint64_t*)tx->d_zsize,
                     (const uint64_t*)tx->d_zsize_part, (const GzState*)S, capacity, d_out, d_member_end, d_summary);
-    if (tx->profile) { (void)rt_event_record(tx->zev[1], st); tx->zev_recorded = true; }
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-    return TGSF_OK;
+    if (tx->profile) tx->zev.end(st);
+    return launched(tx);
 }
 
 extern "C" int tgsf_text_bgzf_deflate_device(tgsf_text* tx, const uint8_t* d_in, uint64_t n_bytes, int eof, uint8_t* d_out, uint64_t out_capacity,
@@ -1264,7 +1250,7 @@ extern "C" int tgsf_text_bgzf_deflate_device(tgsf_text* tx, const uint8_t* d_in,
     if (!d_out) { d_out = tx->d_zout; out_capacity = std::min(out_capacity, tx->max_zout); }
     (void)rt_set_device(tx->device);
     return enqueue_gzout(tx, d_in, n_bytes, eof, d_out, out_capacity, d_member_end, d_summary ? d_summary : tx->d_zsummary,
-                         hip_stream ? (rt_stream)hip_stream : tx->stream);
+                         stream_of(tx, hip_stream));
 }
 
 // deflate what is on the device into the object's compressed buffer, on its stream; summary, bytes and member ends come down
@@ -1272,25 +1258,17 @@ static int gzout_down(tgsf_text* tx, const uint8_t* d_in, uint64_t n_bytes, int 
                       tgsf_text_gzout_summary* out_summary)
 {
     const uint64_t cap = std::min(out_capacity, tx->max_zout);
-    const int e = enqueue_gzout(tx, d_in, n_bytes, eof, tx->d_zout, cap, member_end ? tx->d_zend : nullptr, tx->d_zsummary, tx->stream);
+    int e = enqueue_gzout(tx, d_in, n_bytes, eof, tx->d_zout, cap, member_end ? tx->d_zend : nullptr, tx->d_zsummary, tx->stream);
     if (e) return e;
     tgsf_text_gzout_summary sum;
-    int he = rt_d2h(&sum, tx->d_zsummary, sizeof sum, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    if (tx->profile && tx->zev_recorded) {
-        tx->zev_recorded = false;
-        if (rt_event_ms(&sum.device_ms, tx->zev[0], tx->zev[1])) { (void)rt_last_error(); sum.device_ms = 0.0f; }
-    }
+    if ((e = down(tx, &sum, tx->d_zsummary, sizeof sum))) return e;
+    sum.device_ms = tx->zev.ms(tx->profile);
     if (out_summary) *out_summary = sum;
     if (sum.stop == TGSF_TEXT_CAPACITY)
         return fail(tx, TGSF_E_CAPACITY, "the compressed text has %llu bytes, there is room for %llu (out_capacity %llu, reserved %llu)",
                     (unsigned long long)sum.n_bytes, (unsigned long long)cap, (unsigned long long)out_capacity, (unsigned long long)tx->max_zout);
-    if (sum.n_bytes) he |= rt_d2h(out, tx->d_zout, (size_t)sum.n_bytes, tx->stream);
-    if (member_end && sum.n_members) he |= rt_d2h(member_end, tx->d_zend, (size_t)sum.n_members * 8, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    return TGSF_OK;
+    if ((e = down(tx, out, tx->d_zout, (size_t)sum.n_bytes, false))) return e;
+    return down(tx, member_end, tx->d_zend, member_end ? (size_t)sum.n_members * 8 : 0);
 }
 
 extern "C" int tgsf_text_bgzf_deflate(tgsf_text* tx, const uint8_t* in, uint64_t n_bytes, int eof, uint8_t* out, uint64_t out_capacity,
@@ -1312,11 +1290,9 @@ static int enqueue_crc(tgsf_text* tx, const uint8_t* d_gz, uint32_t n_blocks, co
 {
     const int he = rt_memset(d_bad, 0xFF, 4, st);
     if (he) return fail(tx, TGSF_E_HIP, "device memset failed: %s", rt_errstr(he));
-    const unsigned g = grid_cap(std::min(std::max(blocks_for((uint64_t)n_blocks * kTextLanes, kTextThreads), 1u), 2048u));
     if (n_blocks)
-        TGSF_LAUNCH(k_bgzf_crc, g, kTextThreads, st, d_gz, (const tgsf_text_bgzf_block*)tx->d_gblocks, n_blocks, d_inflated, (const uint32_t*)tx->d_crc_tab, d_bad);
-    if (rt_last_error()) return fail(tx, TGSF_E_HIP, "kernel launch failed");
-    return TGSF_OK;
+        TGSF_LAUNCH(k_bgzf_crc, wave_grid(n_blocks), kTextThreads, st, d_gz, (const tgsf_text_bgzf_block*)tx->d_gblocks, n_blocks, d_inflated, (const uint32_t*)tx->d_crc_tab, d_bad);
+    return launched(tx);
 }
 
 extern "C" int tgsf_text_bgzf_crc_device(tgsf_text* tx, const uint8_t* d_gz, const tgsf_text_bgzf_block* blocks, uint32_t n_blocks,
@@ -1334,7 +1310,7 @@ extern "C" int tgsf_text_bgzf_crc_device(tgsf_text* tx, const uint8_t* d_gz, con
     if (!d_inflated && out > tx->max_bytes) return fail(tx, TGSF_E_CAPACITY, "the members inflate to %llu bytes, the text buffer has %llu", (unsigned long long)out, (unsigned long long)tx->max_bytes);
     (void)rt_set_device(tx->device);
     if (crc_tables_up(tx)) return fail(tx, TGSF_E_HIP, "device allocation failed (the CRC32 tables)");
-    rt_stream st = hip_stream ? (rt_stream)hip_stream : tx->stream;
+    rt_stream st = stream_of(tx, hip_stream);
     const int he = n_blocks ? rt_h2d(tx->d_gblocks, blocks, (size_t)n_blocks * sizeof *blocks, st) : 0;
     if (he) return fail(tx, TGSF_E_HIP, "host to device copy failed: %s", rt_errstr(he));
     return enqueue_crc(tx, d_gz ? d_gz : tx->d_gz, n_blocks, d_inflated ? d_inflated : tx->d_text, d_bad_crc, st);
@@ -1357,13 +1333,11 @@ extern "C" int tgsf_text_bgzf_verify(tgsf_text* tx, const uint8_t* gz, uint64_t 
                     w.n, (unsigned long long)w.out_bytes, tx->max_gblocks, (unsigned long long)tx->max_bytes, (unsigned long long)w.consumed);
     (void)rt_set_device(tx->device);
     if (crc_tables_up(tx)) return fail(tx, TGSF_E_HIP, "device allocation failed (the CRC32 tables)");
-    if ((e = up_inflate(tx, gz, w))) return e;
+    if ((e = up_inflate(tx, gz, w, tx->d_text))) return e;
     if ((e = enqueue_crc(tx, tx->d_gz, w.n, tx->d_text, &tx->d_gstate->bad_crc, tx->stream))) return e;
     BgzfState S;
-    int he = rt_d2h(&S, tx->d_gstate, sizeof S, tx->stream);
-    if (!he) he = rt_sync(tx->stream);
-    if (he) return fail(tx, TGSF_E_HIP, "device to host copy failed: %s", rt_errstr(he));
-    (void)index_ms(tx);
+    if ((e = down(tx, &S, tx->d_gstate, sizeof S))) return e;
+    (void)tx->ev.ms(tx->profile);
     *bad_block = S.bad_block;
     *bad_crc = S.bad_crc;
     if (S.bad_block != 0xFFFFFFFFu) return bad_member(tx, S.bad_block);
@@ -1378,28 +1352,16 @@ extern "C" int tgsf_text_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t
                                      uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary, tgsf_text_summary* in_summary,
                                      const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo, int eof, tgsf_text_gzout_summary* gz_summary)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!text && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, fasta, fastq_out);
-    if (!e) e = check_args(tx, n_bytes, fasta, final);
-    if (!e) e = check_gzout(tx, 0, eof);
-    if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, nullptr, out_summary, 1, eof, gz_summary};
-    return ingest_filter_format(tx, ctx, {text, n_bytes, fasta, final, in_summary, nullptr}, out_index, bo, &to);
+    return filter_call(tx, ctx, {text, n_bytes, fasta, final, in_summary}, out_index, bo, &to);
 }
 
 extern "C" int tgsf_text_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, int final, int fastq_out,
                                          uint8_t* out, uint64_t out_capacity, tgsf_text_out_summary* out_summary, tgsf_text_bam_summary* in_summary,
                                          const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo, int eof, tgsf_text_gzout_summary* gz_summary)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!bam && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, 0, fastq_out);
-    if (!e) e = check_bam(tx, n_bytes, final);
-    if (!e) e = check_gzout(tx, 0, eof);
-    if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, nullptr, out_summary, 1, eof, gz_summary};
-    return ingest_filter_format(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
+    return filter_call(tx, ctx, {bam, n_bytes, 0, final, nullptr, in_summary}, out_index, bo, &to);
 }
 
 extern "C" int tgsf_text_bgzf_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, const uint8_t* gz, uint64_t n_bytes, uint32_t skip, int final, int fastq_out,
@@ -1407,12 +1369,6 @@ extern "C" int tgsf_text_bgzf_bam_filter_bgzf(tgsf_text* tx, tgsf_ctx* ctx, cons
                                               tgsf_text_bgzf_bam_summary* in_summary, const tgsf_text_index_arrays* out_index, tgsf_batch_out* bo,
                                               int eof, tgsf_text_gzout_summary* gz_summary)
 {
-    if (!tx) return TGSF_E_INVALID;
-    if (!ctx || !out_summary || !in_summary || (bo && !bo->reads) || (!gz && n_bytes) || (!out && out_capacity)) return fail(tx, TGSF_E_INVALID, "null argument");
-    int e = check_format(tx, 0, 0, fastq_out);
-    if (!e) e = check_bgzf_bam(tx, n_bytes, final);
-    if (!e) e = check_gzout(tx, 0, eof);
-    if (e) return e;
     const FormatTo to = {fastq_out, out, out_capacity, nullptr, out_summary, 1, eof, gz_summary};
-    return ingest_filter_format(tx, ctx, {gz, n_bytes, 0, final, nullptr, &in_summary->bam, in_summary, skip}, out_index, bo, &to);
+    return filter_call(tx, ctx, {gz, n_bytes, 0, final, nullptr, nullptr, in_summary, skip}, out_index, bo, &to);
 }
